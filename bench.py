@@ -26,7 +26,14 @@ priced by its ALGORITHMIC bytes per launch:
 `traffic` comes from the rocprofv3 PMC passes committed under profiles/
 (profiles/<round>/pmc_traffic.json, written by profiles/collect_pmc.py).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+A plain run sets up, warms up, times the K steps and prints the headline
+line.  --full adds every other section (per-kernel split + roofline + parity
+spot check of the step, the spf_table path at N = 1, WAN all-sources, what-if
+batch, RouteDb loops, CPU baselines).  --dump-outputs DIR writes what the last
+timed step computed, for a fixed seeded sample of sources, as DIR/*.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                       [--full [--no-cpu-baseline] [--no-wan] ...]
 """
 
 from __future__ import annotations
@@ -64,6 +71,13 @@ def parse():
                         "torch.distributed.run this script starts the N rank processes itself")
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed (distance rows and "
+                        "next-hop masks of a fixed, seeded sample of sources) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: per-kernel split, roofline and parity spot check of the "
+                        "step, the spf_table path, WAN all-sources, what-if batch, RouteDb sections and "
+                        "CPU baselines (each can be switched off with its --no-* option); minutes")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-full", action="store_true",
                    help="time BASELINE.md §3 line A fully on all host cores: config 2 (every fabric "
@@ -1550,6 +1564,49 @@ def _timed_table(t, steps, warmup, dist):
     return (time.perf_counter() - t0) * 1000.0 / steps, t.elapsed_ms()
 
 
+DUMP_SEED = 20240607
+DUMP_SOURCES = 64
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_sample(first, count, V, words_of):
+    """The sources --dump-outputs writes: a fixed, seeded sample of the
+    `count` sources from `first` on (the same for every run with the same
+    arguments), cut so that the float64 files stay under DUMP_MAX_BYTES.
+    words_of(i) = u64 mask words per node of source i."""
+    import numpy as np
+
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.sort(rng.choice(count, size=min(DUMP_SOURCES, count), replace=False)) + first
+    while len(pick) > 1:
+        W = max(words_of(int(i)) for i in pick)
+        if len(pick) * (V * 8 * (1 + 2 * W) + 8) <= DUMP_MAX_BYTES:
+            break
+        pick = pick[: len(pick) // 2]
+    return pick
+
+
+def dump_outputs(dirname, sources, pick, rows, masks):
+    """DIR/sources.npy [S], DIR/dist.npy [S, V] and DIR/nexthop_masks.npy
+    [S, V, 2 * W], all float64 and exact: rows[k] is source pick[k]'s
+    distance row, masks[k] its [V, W_k] u64 next-hop mask words, written as
+    (low, high) 32-bit halves and zero-padded to the widest sampled source."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    S, V = len(pick), len(rows[0])
+    W = max(m.shape[1] for m in masks)
+    d = np.stack([np.asarray(r).astype(np.float64) for r in rows])
+    nh = np.zeros((S, V, 2 * W), dtype=np.float64)
+    for k, m in enumerate(masks):
+        m = np.asarray(m, dtype=np.uint64)
+        nh[k, :, 0:2 * m.shape[1]:2] = (m & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        nh[k, :, 1:2 * m.shape[1]:2] = (m >> np.uint64(32)).astype(np.float64)
+    np.save(os.path.join(dirname, "sources.npy"), np.asarray(sources)[pick].astype(np.float64))
+    np.save(os.path.join(dirname, "dist.npy"), d)
+    np.save(os.path.join(dirname, "nexthop_masks.npy"), nh)
+
+
 def fabric_sharded(args, topo, world, rank, local, dist, cluster):
     """N > 1 headline: STRONG scaling of the one 9,976-source fabric table.
     The engine splits the sources into contiguous blocks, one per GPU
@@ -1568,18 +1625,27 @@ def fabric_sharded(args, topo, world, rank, local, dist, cluster):
     sources = np.arange(V, dtype=np.uint32)
     t = abi.Table(cluster, csr, sources, abi.SPF_F_NEXTHOPS)
     step_ms, (comp_ms, _) = _timed_table(t, args.steps, args.warmup, dist)
-    tg = abi.Table(cluster, csr, sources, abi.SPF_F_NEXTHOPS | abi.SPF_T_GATHER_ROWS)
-    gstep_ms, (gcomp_ms, gather_ms) = _timed_table(tg, max(3, args.steps // 2), 1, dist)
+    first, count = t.block(cluster.first_rank)
+    if args.dump_outputs and rank == 0:
+        # rank 0's own block of the table the timed steps wrote
+        pick = dump_sample(first, count, V, t.nh_words)
+        dump_outputs(args.dump_outputs, sources, pick,
+                     [t.fetch_rows(int(i), 1)[0] for i in pick],
+                     [t.fetch_nexthops(int(i), 1).reshape(V, t.nh_words(int(i))) for i in pick])
+    tg = None
+    gstep_ms = gather_ms = 0.0
+    if args.full:
+        tg = abi.Table(cluster, csr, sources, abi.SPF_F_NEXTHOPS | abi.SPF_T_GATHER_ROWS)
+        gstep_ms, (gcomp_ms, gather_ms) = _timed_table(tg, max(3, args.steps // 2), 1, dist)
     red = torch.tensor([step_ms, comp_ms, gstep_ms, gather_ms], dtype=torch.float64,
                        device=f"cuda:{local}")
     if dist:
         dist.all_reduce(red, op=dist.ReduceOp.MAX)
     step_ms, comp_ms, gstep_ms, gather_ms = (float(x) for x in red)
-    first, count = t.block(cluster.first_rank)
     # parity (rank 0): rows + next hops of its own block, and rows of the LAST
     # rank's block read from the gathered copy, against the DijkstraQ replay
     check = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import spf_py
 
         bad = 0
@@ -1607,7 +1673,20 @@ def fabric_sharded(args, topo, world, rank, local, dist, cluster):
         check = "ok" if bad == 0 else f"{bad} mismatches"
     kernel = t.kernel(0)
     t.close()
-    tg.close()
+    if tg is not None:
+        tg.close()
+    more = {}
+    if args.full:
+        more = {
+            "with_row_gather": {
+                "what": "the same table with every GPU's uint32 distance rows all-gathered over xGMI "
+                        "(in-place ncclAllGather inside spf_table_run)",
+                "ms_per_step": round(gstep_ms, 4), "gather_ms": round(gather_ms, 4),
+                "value": round(V / (gstep_ms / 1000.0), 1),
+                "gathered_bytes": int(V * V * 4),
+            },
+            "parity_spot_check": check,
+        }
     return {
         "metric": "all-sources SPF/sec + GTEPS on 10k-node fabric; full RouteDb rebuild ms",
         "value": round(V / (step_ms / 1000.0), 1),
@@ -1633,22 +1712,15 @@ def fabric_sharded(args, topo, world, rank, local, dist, cluster):
             "value": round(V * E / (step_ms / 1000.0) / 1e9, 2),
             "note": "per-source-equivalent (sources x directed edges / step), not a measured rate"}},
         "device_compute_ms": round(comp_ms, 4),
-        "with_row_gather": {
-            "what": "the same table with every GPU's uint32 distance rows all-gathered over xGMI "
-                    "(in-place ncclAllGather inside spf_table_run)",
-            "ms_per_step": round(gstep_ms, 4), "gather_ms": round(gather_ms, 4),
-            "value": round(V / (gstep_ms / 1000.0), 1),
-            "gathered_bytes": int(V * V * 4),
-        },
-        "parity_spot_check": check,
+        **more,
         "communicator": {"world": int(cluster.world), "first_rank": int(cluster.first_rank),
                          "local_devices": int(cluster.local_devices)},
     }
 
 
 def fabric_single(args, topo, world, rank, local, dist):
-    """N = 1 headline: the fabric all-sources step as one query on one GPU,
-    with the per-kernel split and roofline."""
+    """N = 1 headline: the fabric all-sources step as one query on one GPU
+    (--full: with the per-kernel split and roofline, _single_details)."""
     import numpy as np
     import torch
 
@@ -1685,11 +1757,6 @@ def fabric_single(args, topo, world, rank, local, dist):
         dist.barrier()
     wall = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps
-    # per-kernel device time of the timed launches (engine-side HIP events on
-    # the same stream, recorded around each kernel)
-    hist = q.stage_history(args.steps)
-    d_ms = sum(h[0] for h in hist) / max(1, len(hist))
-    n_ms = sum(h[1] for h in hist) / max(1, len(hist))
     step_ms = wall * 1000.0 / args.steps
     if dist:
         t = torch.tensor([step_ms, kernel_ms], device="cuda", dtype=torch.float64)
@@ -1699,6 +1766,64 @@ def fabric_single(args, topo, world, rank, local, dist):
     nsrc = len(sources)
     E = len(csr.col)
     value = world * nsrc / (step_ms / 1000.0)
+    kname = q.kernel
+    if args.dump_outputs and rank == 0:
+        pick = dump_sample(0, nsrc, csr.num_nodes, q.nh_words)
+        dump_outputs(args.dump_outputs, sources, pick, [q.dist(int(i)) for i in pick],
+                     [q.nexthops(int(i)) for i in pick])
+
+    out = {
+        "metric": "all-sources SPF/sec + GTEPS on 10k-node fabric; full RouteDb rebuild ms",
+        "value": round(value, 1),
+        "unit": "SPF/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(step_ms, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic fabric (DecisionBenchmark createFabric, SSW bug fixed), metric 1",
+        "config": {
+            "workload": "fabric_full all-sources SPF + ECMP next-hop sets (BASELINE configs[1])",
+            "nodes": csr.num_nodes,
+            "links": int(csr.num_links),
+            "directed_edges": E,
+            "sources_per_gpu": nsrc,
+            "kernel": kname,
+            "parallelism": "one table of every source on one GPU (N > 1 runs fabric_sharded)",
+        },
+        "derived": {"gteps_equivalent": {
+            "value": round(world * nsrc * E / (step_ms / 1000.0) / 1e9, 2),
+            "note": "per-source-equivalent, not a measured rate: sources x directed edges per step "
+                    "time (a textbook SSSP traverses every edge once); the bit-parallel BFS scans an "
+                    "edge once per level for 64 sources, so this counts shared scans, not traffic"}},
+        "kernel_ms": round(kernel_ms, 4),
+        "kernels_launched": q.kernels(),
+    }
+    if args.full:
+        out.update(_single_details(args, q, csr, sources, nh_bytes, step_ms, rank))
+    q.close()
+    g.close()
+    return out
+
+
+def _single_details(args, q, csr, sources, nh_bytes, step_ms, rank):
+    """--full: the per-kernel split of the timed launches, the roofline of
+    the dominant kernel, the step's output floor and the parity spot check
+    (none of them launches a kernel of its own)."""
+    import numpy as np
+
+    from openr_amd import abi
+
+    # per-kernel device time of the timed launches (engine-side HIP events on
+    # the same stream, recorded around each kernel)
+    hist = q.stage_history(args.steps)
+    d_ms = sum(h[0] for h in hist) / max(1, len(hist))
+    n_ms = sum(h[1] for h in hist) / max(1, len(hist))
+    nsrc = len(sources)
+    E = len(csr.col)
     kname = q.kernel
     dist_k, nh_k = KERNELS.get(kname, (kname, None))
     # the kernels the run actually launched (spf_query_kernels): the MS-BFS
@@ -1763,36 +1888,8 @@ def fabric_single(args, topo, world, rank, local, dist):
                     bad += d[v] != np.uint64(abi.SPF_UNREACHABLE)
         check = "ok" if bad == 0 else f"{bad} mismatches"
 
-    out = {
-        "metric": "all-sources SPF/sec + GTEPS on 10k-node fabric; full RouteDb rebuild ms",
-        "value": round(value, 1),
-        "unit": "SPF/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(step_ms, 4),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic fabric (DecisionBenchmark createFabric, SSW bug fixed), metric 1",
-        "config": {
-            "workload": "fabric_full all-sources SPF + ECMP next-hop sets (BASELINE configs[1])",
-            "nodes": csr.num_nodes,
-            "links": int(csr.num_links),
-            "directed_edges": E,
-            "sources_per_gpu": nsrc,
-            "kernel": kname,
-            "parallelism": "one table of every source on one GPU (N > 1 runs fabric_sharded)",
-        },
-        "derived": {"gteps_equivalent": {
-            "value": round(world * nsrc * E / (step_ms / 1000.0) / 1e9, 2),
-            "note": "per-source-equivalent, not a measured rate: sources x directed edges per step "
-                    "time (a textbook SSSP traverses every edge once); the bit-parallel BFS scans an "
-                    "edge once per level for 64 sources, so this counts shared scans, not traffic"}},
-        "kernel_ms": round(kernel_ms, 4),
+    return {
         "kernels": stages,
-        "kernels_launched": launched,
         "parity_spot_check": check,
         "roofline": _roofline(dom, dom_ms, dom_bytes, traffic, traffic_src),
         "step_output_floor": {
@@ -1803,9 +1900,6 @@ def fabric_single(args, topo, world, rank, local, dist):
             "frac": round(floor_bytes / (step_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
         },
     }
-    q.close()
-    g.close()
-    return out
 
 
 class RankLaunchError(RuntimeError):
@@ -1895,6 +1989,24 @@ def launch_ranks(n: int, argv, script=None) -> int:
     return 0
 
 
+def _table_path(args, topo, local):
+    """--full: the N > 1 code path at N = 1 (spf_table over a one-rank RCCL
+    cluster), so the 1 -> N curve has a same-code N = 1 point beside the
+    headline query."""
+    try:
+        c1 = cluster_for(1, 0, local, None)
+        sub = argparse.Namespace(**dict(vars(args), dump_outputs=None))
+        tl = fabric_sharded(sub, topo, 1, 0, local, None, c1)
+        c1.close()
+        out = {k: tl[k] for k in ("value", "unit", "ms_per_step", "device_compute_ms",
+                                  "with_row_gather", "parity_spot_check", "communicator")}
+        out["what"] = ("the headline workload through spf_table over a one-rank "
+                       "RCCL cluster: the code path of every N > 1 line")
+        return out
+    except Exception as e:  # reported, never silently replaced
+        return {"error": repr(e)}
+
+
 def main():
     args = parse()
     try:
@@ -1934,20 +2046,11 @@ def main():
     else:
         cluster = None
         out = fabric_single(args, topo, world, rank, local, dist)
-        # the N > 1 code path at N = 1 (spf_table over a one-rank RCCL
-        # cluster), so the 1 -> N curve has a same-code N = 1 point beside
-        # the headline query
-        try:
-            c1 = cluster_for(1, 0, local, None)
-            tl = fabric_sharded(args, topo, 1, 0, local, None, c1)
-            c1.close()
-            out["table_path"] = {k: tl[k] for k in ("value", "unit", "ms_per_step", "device_compute_ms",
-                                                    "with_row_gather", "parity_spot_check",
-                                                    "communicator")}
-            out["table_path"]["what"] = ("the headline workload through spf_table over a one-rank "
-                                         "RCCL cluster: the code path of every N > 1 line")
-        except Exception as e:  # reported, never silently replaced
-            out["table_path"] = {"error": repr(e)}
+        if args.full:
+            out["table_path"] = _table_path(args, topo, local)
+    if not args.full:
+        # a plain run is the headline alone: every other section is --full's
+        args.no_wan = args.no_whatif = args.no_route_db = args.no_cpu_baseline = True
     if not args.no_wan:
         try:
             if cluster is not None:

@@ -6,7 +6,7 @@ MI355X guide requires), e.g.:
   cd /tmp && export TMPDIR=/tmp
   timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -T -d $R/gpurun_out/pmc_fetch \
       -o run --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 \
-      --no-route-db --no-cpu-baseline
+      --full --no-route-db --no-cpu-baseline
   timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -T -d $R/gpurun_out/pmc_write ...
   python $R/profiles/collect_pmc.py $R/gpurun_out/pmc_fetch $R/gpurun_out/pmc_write \
       $R/profiles/r01/pmc_traffic.json

@@ -10,7 +10,7 @@ TAG=${1:-r01}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT/final
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline --no-route-db --no-whatif"
+B="$R/bench.py --full --no-cpu-baseline --no-route-db --no-whatif"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -d $OUT/trace -o run --output-format csv -- \
   python3 $B --steps 10 --warmup 3 > $OUT/trace_bench.json
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -T -d $OUT/pmc_fetch -o run --output-format csv -- \

@@ -9,7 +9,7 @@ TAG=${1:-r01}
 OUT=$R/gpurun_out/prof_rdb_$TAG
 mkdir -p $OUT/final
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline --no-wan --no-whatif"
+B="$R/bench.py --full --no-cpu-baseline --no-wan --no-whatif"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -T -d $OUT/trace -o run --output-format csv -- \
   python3 $B --steps 5 --warmup 2 > $OUT/trace_bench.json
 timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE -T -d $OUT/pmc_fetch -o run --output-format csv -- \

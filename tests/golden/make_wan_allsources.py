@@ -28,8 +28,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
-OUT = os.path.join(HERE, "wan100k_allsources.npz")
-
 
 def main():
     from oracle import build as OB
@@ -66,8 +64,12 @@ def main():
         if s < n:
             assert (S[s] == Sg[i]).all(), int(s)
     if n == V:
-        np.savez_compressed(OUT, summary=S)
-        print("wrote", OUT, flush=True)
+        # two halves of the source range, so that no committed file passes 1 MiB
+        from tests.golden.summary import WAN100K_PARTS
+
+        for f, part in zip(WAN100K_PARTS, (S[: V // 2], S[V // 2:])):
+            np.savez_compressed(os.path.join(HERE, f), summary=part)
+            print("wrote", os.path.join(HERE, f), flush=True)
     print(f"done in {time.time() - t0:.0f}s", flush=True)
 
 

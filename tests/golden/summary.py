@@ -117,11 +117,23 @@ def summaries_from_rows(rows32, masks, words, nbrs, mix_rows=()):
     return out
 
 
+WAN100K_PARTS = ("wan100k_allsources_0.npz", "wan100k_allsources_1.npz")
+
+
+def load_wan100k_summary():
+    """The 100,000-row WAN golden, uint64 [100000, 4]: stored as two halves
+    of the source range (tests/golden/make_wan_allsources.py), joined here."""
+    import os
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    return np.concatenate([np.load(os.path.join(here, f))["summary"] for f in WAN100K_PARTS])
+
+
 def dist_summaries_torch(rows):
     """(reached, sum_dist, 0, mix) of distance-only rows, computed where the
     rows live: `rows` is an int32 torch tensor [Q, V] (-1 = unreached, the
     uint32 rows reinterpreted), on any device — the checker side of the
-    100,000-row WAN golden (tests/golden/wan100k_allsources.npz) without
+    100,000-row WAN golden (tests/golden/wan100k_allsources_*.npz) without
     copying 40 GB to the host.  uint64 arithmetic is done in int64 (two's
     complement: sums and products wrap mod 2^64 alike, right shifts are
     masked to be logical).  Returns uint64 [Q, 4] numpy."""

@@ -42,6 +42,49 @@ def test_check_world_rules():
         bench.check_world(0, env={}, devices=8)
 
 
+def test_dump_outputs_sample_is_fixed_and_files_exact(tmp_path):
+    import numpy as np
+
+    V, n = 50, 300
+    words = lambda i: 1 + (i % 3)  # noqa: E731
+    pick = bench.dump_sample(0, n, V, words)
+    assert len(pick) == bench.DUMP_SOURCES == len(set(pick.tolist()))
+    assert (pick == bench.dump_sample(0, n, V, words)).all() and (np.diff(pick) > 0).all()
+    assert (bench.dump_sample(100, n, V, words) == pick + 100).all()
+    # a sample too large for the size limit is cut, never the limit raised
+    big = bench.dump_sample(0, n, 100_000, lambda i: 2)
+    assert 1 <= len(big) < bench.DUMP_SOURCES
+    assert len(big) * 100_000 * 8 * 5 <= bench.DUMP_MAX_BYTES
+    assert (big == pick[: len(big)]).all()
+    rng = np.random.default_rng(1)
+    rows = [rng.integers(0, 2**32, V, dtype=np.uint64) for _ in pick]
+    rows[0][3] = np.uint64(2**64 - 1)
+    masks = [rng.integers(0, 2**64, (V, words(int(i))), dtype=np.uint64) for i in pick]
+    bench.dump_outputs(str(tmp_path / "d"), np.arange(n, dtype=np.uint32), pick, rows, masks)
+    src = np.load(tmp_path / "d" / "sources.npy")
+    d = np.load(tmp_path / "d" / "dist.npy")
+    nh = np.load(tmp_path / "d" / "nexthop_masks.npy")
+    assert src.dtype == d.dtype == nh.dtype == np.float64
+    assert (src == pick).all() and d.shape == (len(pick), V) and nh.shape == (len(pick), V, 6)
+    assert (d[1] == rows[1].astype(np.float64)).all() and d[0][3] == float(2**64)
+    for k, m in enumerate(masks):
+        W = m.shape[1]
+        back = nh[k, :, 0:2 * W:2].astype(np.uint64) | (nh[k, :, 1:2 * W:2].astype(np.uint64) << np.uint64(32))
+        assert (back == m).all() and not nh[k, :, 2 * W:].any()
+
+
+def test_plain_run_options():
+    argv, sys.argv = sys.argv, ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+    try:
+        a = bench.parse()
+        assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+        sys.argv += ["--full", "--dump-outputs", "x"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "x"
+    finally:
+        sys.argv = argv
+
+
 RANK_SCRIPT = textwrap.dedent("""
     import json, os, sys
     import torch, torch.distributed as dist

@@ -114,9 +114,10 @@ def test_config3_wan100k_all_sources_sharded(gpu_ready):
     # EVERY row against the 100,000-source golden (oracle/csr_spf.h,
     # tests/golden/make_wan_allsources.py): (reached, sum, mix) per source,
     # summarised on the device in 2,048-row slices
-    from tests.golden.summary import dist_summaries_torch
+    from tests.golden.summary import dist_summaries_torch, load_wan100k_summary
 
-    want = np.load(os.path.join(GOLD, "wan100k_allsources.npz"))["summary"]
+    want = load_wan100k_summary()
+    assert want.shape == (V, 4)
     bad = []
     for lo in range(0, V, 2048):
         got = dist_summaries_torch(sas.table[lo:min(V, lo + 2048)])

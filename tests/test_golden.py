@@ -82,7 +82,7 @@ def test_oracle_matches_reference_wan_checksum(oracle):
 
 
 def test_wan100k_allsources_golden_pins(oracle):
-    """tests/golden/wan100k_allsources.npz (every one of the 100,000 WAN
+    """tests/golden/wan100k_allsources_*.npz (every one of the 100,000 WAN
     sources, oracle/csr_spf.h) agrees with the reference's own checksum of
     row n0 and with 3 of the committed sha256 rows recomputed here; the
     torch summariser the GPU test uses equals the oracle's rows_summary."""
@@ -91,9 +91,9 @@ def test_wan100k_allsources_golden_pins(oracle):
     import torch
 
     from openr_amd import topologies as TP
-    from tests.golden.summary import dist_summaries_torch
+    from tests.golden.summary import dist_summaries_torch, load_wan100k_summary
 
-    S = np.load(os.path.join(GOLD, "wan100k_allsources.npz"))["summary"]
+    S = load_wan100k_summary()
     assert S.shape == (100000, 4) and S.dtype == np.uint64
     assert (S[:, 0] == 100000).all() and (S[:, 2] == 0).all()  # connected, distances only
     anchor = [a for a in _gold("wan_anchors.json")["anchors"] if a["V"] == 100000 and a["S"] == 1][0]
