@@ -276,6 +276,36 @@ int spf_query_trace_paths(
  * ends[] holds Σ path_count end offsets, each relative to its query's first
  * link. */
 int spf_query_trace_fetch(spf_query* q, uint32_t* links, uint32_t* ends);
+/* selectKsp2's walk over the traced paths on the device (Decision.cpp:970-
+ * 1011 without the prepend label): per path the sum of the directional link
+ * metrics from the query's source (always the link metric, also for a
+ * SPF_F_UNIT_METRIC query), and the node labels of its hops after the first
+ * in PUSH-stack order -- the destination's label first, the second node's
+ * last; links - 1 of them.  node_labels: [V] host array.  Call after
+ * spf_query_trace_paths (before or after spf_query_trace_fetch), valid until
+ * the next trace or run; SPF_E_INVALID when there is no trace since the last
+ * run, SPF_E_UNSUPPORTED for 64-bit rows and for a graph patched by
+ * spf_graph_set_edges.  A path whose link id is >= num_links, whose link
+ * lacks a half-edge or is not incident to the node the walk is at gets
+ * cost SPF_EXPAND_INVALID and zero labels (never a device-traced path).
+ * spf_query_trace_expand_fetch packs like spf_query_trace_fetch (overflowed
+ * queries skipped): cost[Σ path_count], labels[Σ (link_count - path_count)],
+ * the labels of path p of a query at (its first link) - p from the query's
+ * label base. */
+#define SPF_EXPAND_INVALID UINT64_MAX
+int spf_query_trace_expand(spf_query* q, const int32_t* node_labels);
+int spf_query_trace_expand_fetch(spf_query* q, uint64_t* cost, int32_t* labels);
+/* The same kernel over caller-supplied paths of one graph (k = 1 paths
+ * traced on the host): path i starts at node sources[i] and takes
+ * links[off[i] .. off[i + 1]).  cost[num_paths]; labels[Σ max(len_i - 1, 0)]
+ * in path order (= off[n] - n entries, path i at off[i] - i, while no path
+ * is empty).  An empty path is invalid (SPF_EXPAND_INVALID, no labels).
+ * SPF_E_INVALID for sources[i] >= V or descending offsets.  Metrics are
+ * read at 64 bits, so every graph is supported but one patched by
+ * spf_graph_set_edges (SPF_E_UNSUPPORTED). */
+int spf_graph_expand_paths(
+    spf_graph* g, uint32_t num_paths, const uint32_t* sources, const uint32_t* off,
+    const uint32_t* links, const int32_t* node_labels, uint64_t* cost, int32_t* labels);
 
 /* ---- incremental all-sources tables ----
  * The reference drops every memoized SpfResult on any topology change
@@ -477,6 +507,10 @@ int spf_table_fetch_nexthops(spf_table* t, uint32_t first, uint32_t count, uint6
 int spf_table_trace_paths(
     spf_table* t, const uint32_t* dests, uint32_t* path_count, uint32_t* link_count);
 int spf_table_trace_fetch(spf_table* t, uint32_t* links, uint32_t* ends);
+/* spf_query_trace_expand / _expand_fetch over every local block, after
+ * spf_table_trace_paths; costs and labels packed in table-query order. */
+int spf_table_trace_expand(spf_table* t, const int32_t* node_labels);
+int spf_table_trace_expand_fetch(spf_table* t, uint64_t* cost, int32_t* labels);
 /* Gathered buffers on local device `local`: rows [world * cap][V] uint32
  * (cap = ceil(n / world)), masks [world * mask_cap] bytes in the layout of
  * spf_table_layout; NULL when that gather is off. */

@@ -25,6 +25,7 @@ SPF_E_DEVICE = -3
 SPF_E_UNSUPPORTED = -4
 SPF_UNREACHABLE = (1 << 64) - 1
 SPF_TRACE_OVERFLOW = 0xFFFFFFFF
+SPF_EXPAND_INVALID = (1 << 64) - 1
 SPF_F_UNIT_METRIC = 0x1
 SPF_F_NEXTHOPS = 0x2
 SPF_F_ORDER = 0x4
@@ -75,6 +76,9 @@ EXPORTED_SYMBOLS = (
     "spf_query_fetch_host",
     "spf_query_trace_paths",
     "spf_query_trace_fetch",
+    "spf_query_trace_expand",
+    "spf_query_trace_expand_fetch",
+    "spf_graph_expand_paths",
     "spf_graph_diff",
     "spf_table_screen",
     "spf_query_scatter_rows",
@@ -106,6 +110,8 @@ EXPORTED_SYMBOLS = (
     "spf_table_fetch_nexthops",
     "spf_table_trace_paths",
     "spf_table_trace_fetch",
+    "spf_table_trace_expand",
+    "spf_table_trace_expand_fetch",
     "spf_table_device_buffers",
     "spf_table_kernel_name",
     "spf_cgraph_create",
@@ -231,6 +237,7 @@ def load():
     u32 = C.c_uint32
     pu32 = C.POINTER(C.c_uint32)
     pu64 = C.POINTER(C.c_uint64)
+    pi32 = C.POINTER(C.c_int32)
     sig = {
         "spf_device_count": (C.c_int, []),
         "spf_error_string": (C.c_char_p, [C.c_int]),
@@ -278,6 +285,9 @@ def load():
         "spf_query_fetch_host": (C.c_int, [vp, u32, u32, vp, C.c_size_t, vp]),
         "spf_query_trace_paths": (C.c_int, [vp, u32, u32, pu32, pu32, pu32]),
         "spf_query_trace_fetch": (C.c_int, [vp, pu32, pu32]),
+        "spf_query_trace_expand": (C.c_int, [vp, pi32]),
+        "spf_query_trace_expand_fetch": (C.c_int, [vp, pu64, pi32]),
+        "spf_graph_expand_paths": (C.c_int, [vp, u32, pu32, pu32, pu32, pi32, pu64, pi32]),
         "spf_query_device_rows": (
             C.c_int,
             [vp, C.POINTER(vp), pu32, C.POINTER(vp), pu64],
@@ -313,6 +323,8 @@ def load():
         "spf_table_fetch_nexthops": (C.c_int, [vp, u32, u32, pu64]),
         "spf_table_trace_paths": (C.c_int, [vp, pu32, pu32, pu32]),
         "spf_table_trace_fetch": (C.c_int, [vp, pu32, pu32]),
+        "spf_table_trace_expand": (C.c_int, [vp, pi32]),
+        "spf_table_trace_expand_fetch": (C.c_int, [vp, pu64, pi32]),
         "spf_table_device_buffers": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(vp), pu64]),
         "spf_table_kernel_name": (C.c_int, [vp, u32, C.POINTER(C.c_char_p)]),
         "spf_cgraph_create": (C.c_int, [vp, C.POINTER(_GraphDesc), C.POINTER(vp)]),
@@ -447,6 +459,33 @@ class Graph:
         ov = np.ascontiguousarray(overloaded, dtype=np.uint8)
         _check(load().spf_graph_set_transit(self.h, _p(ov, C.c_uint8)), "transit")
 
+    def expand_paths(self, sources, paths, node_labels):
+        """spf_graph_expand_paths: path i (a list of link ids) walked from
+        sources[i].  Returns [(cost or None, [labels])]: None marks an invalid
+        path (its labels are zeros)."""
+        if len(node_labels) != self.V:
+            raise ValueError("node_labels: one label per node")
+        src = np.ascontiguousarray(sources, dtype=np.uint32)
+        if len(src) != len(paths):
+            raise ValueError("sources / paths length mismatch")
+        off = np.zeros(len(paths) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(p) for p in paths])
+        flat = [int(l) for p in paths for l in p]
+        links = np.asarray(flat if flat else [0], dtype=np.uint32)
+        nl = np.ascontiguousarray(node_labels, dtype=np.int32)
+        lens = [max(len(p) - 1, 0) for p in paths]
+        cost = np.zeros(max(len(paths), 1), dtype=np.uint64)
+        lab = np.zeros(max(sum(lens), 1), dtype=np.int32)
+        _check(load().spf_graph_expand_paths(
+            self.h, len(paths), _p(src, C.c_uint32), _p(off, C.c_uint32), _p(links, C.c_uint32),
+            _p(nl, C.c_int32), _p(cost, C.c_uint64), _p(lab, C.c_int32)), "expand_paths")
+        out, lo = [], 0
+        for i, n in enumerate(lens):
+            c = int(cost[i])
+            out.append((None if c == SPF_EXPAND_INVALID else c, [int(x) for x in lab[lo : lo + n]]))
+            lo += n
+        return out
+
     def set_edges(self, edges, up, metrics):
         """Half-edges down (up=0) / back up (1) in place (spf_graph_set_edges)."""
         e = np.ascontiguousarray(edges, dtype=np.uint32)
@@ -567,6 +606,35 @@ def _unpack_traces(n, pc, lc, fetch):
         out.append(paths)
         lo += int(lc[i])
         po += int(pc[i])
+    return out
+
+
+def _expand_traces(traced, labels, expand, fetch, check):
+    """Shared body of Query / Table.trace_expand.  `traced`: what the handle's
+    last trace_paths returned (None: no trace yet, which the C call reports).
+    Per query None (overflow) or [(cost, [labels])] per path; cost is None
+    for an invalid path (SPF_EXPAND_INVALID)."""
+    nl = np.ascontiguousarray(labels, dtype=np.int32)
+    check(expand(_p(nl, C.c_int32)), "trace_expand")
+    if traced is None:
+        raise SpfError("trace_expand: no trace_paths call on this handle")
+    lens = [len(p) for paths in traced if paths is not None for p in paths]
+    cost = np.zeros(max(len(lens), 1), dtype=np.uint64)
+    lab = np.zeros(max(sum(lens) - len(lens), 1), dtype=np.int32)
+    check(fetch(_p(cost, C.c_uint64), _p(lab, C.c_int32)), "trace_expand_fetch")
+    out, po, lo = [], 0, 0
+    for paths in traced:
+        if paths is None:
+            out.append(None)
+            continue
+        one = []
+        for p in paths:
+            c = int(cost[po])
+            one.append((None if c == SPF_EXPAND_INVALID else c,
+                        [int(x) for x in lab[lo : lo + len(p) - 1]]))
+            po += 1
+            lo += len(p) - 1
+        out.append(one)
     return out
 
 
@@ -748,8 +816,23 @@ class Query:
         lib = load()
         _check(lib.spf_query_trace_paths(self.h, first, n, _p(d, C.c_uint32), _p(pc, C.c_uint32),
                                          _p(lc, C.c_uint32)), "trace_paths")
-        return _unpack_traces(n, pc, lc, lambda L, E: _check(
+        self._traced = None
+        self._traced = _unpack_traces(n, pc, lc, lambda L, E: _check(
             lib.spf_query_trace_fetch(self.h, _p(L, C.c_uint32), _p(E, C.c_uint32)), "trace_fetch"))
+        return self._traced
+
+    def trace_expand(self, node_labels):
+        """spf_query_trace_expand + _expand_fetch over the last trace_paths
+        call: per query None (overflow) or, per path in trace_paths' order,
+        (cost, [labels]) -- the link-metric sum and the PUSH stack of the hops
+        after the first, destination's label first (no prepend label)."""
+        lib = load()
+        if len(node_labels) != self.graph.V:
+            raise ValueError("node_labels: one label per node")
+        return _expand_traces(
+            getattr(self, "_traced", None), node_labels,
+            lambda nl: lib.spf_query_trace_expand(self.h, nl),
+            lambda c, l: lib.spf_query_trace_expand_fetch(self.h, c, l), _check)
 
     def device_rows(self):
         dp = C.c_void_p()
@@ -965,9 +1048,22 @@ class Table:
         lib = load()
         _check_cl(lib.spf_table_trace_paths(self.h, _p(d, C.c_uint32), _p(pc, C.c_uint32),
                                             _p(lc, C.c_uint32)), "spf_table_trace_paths")
-        return _unpack_traces(n, pc, lc, lambda L, E: _check_cl(
+        self._traced = None
+        self._traced = _unpack_traces(n, pc, lc, lambda L, E: _check_cl(
             lib.spf_table_trace_fetch(self.h, _p(L, C.c_uint32), _p(E, C.c_uint32)),
             "spf_table_trace_fetch"))
+        return self._traced
+
+    def trace_expand(self, node_labels):
+        """spf_table_trace_expand + _expand_fetch: Query.trace_expand's result
+        per table query."""
+        lib = load()
+        if len(node_labels) != self.V:
+            raise ValueError("node_labels: one label per node")
+        return _expand_traces(
+            getattr(self, "_traced", None), node_labels,
+            lambda nl: lib.spf_table_trace_expand(self.h, nl),
+            lambda c, l: lib.spf_table_trace_expand_fetch(self.h, c, l), _check_cl)
 
     def device_buffers(self, local: int = 0):
         r, m = C.c_void_p(), C.c_void_p()

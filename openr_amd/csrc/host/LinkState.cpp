@@ -929,7 +929,19 @@ struct DeviceTraces {
   std::vector<uint32_t> links, ends;      // packed (spf_query_trace_fetch)
   std::vector<std::unique_ptr<SpfView>> rows; // overflowed queries only
   bool unsupported = false; // 64-bit rows in some block: use runBatchAuto
+  // spf_query_trace_expand_fetch's arrays (nodeLabels given): cost per path,
+  // labels[links - paths]
+  bool expanded = false;
+  std::vector<uint64_t> cost;
+  std::vector<int32_t> labels;
 };
+
+// opt-in (OPENR_KSP2_DEVICE_EXPAND=1): the traced paths' costs and label
+// stacks from spf_path_expand_kernel instead of selectKsp2's walk per prefix
+bool deviceExpandEnabled() {
+  const char* e = std::getenv("OPENR_KSP2_DEVICE_EXPAND");
+  return e && std::atoi(e) != 0;
+}
 
 // default (OPENR_KSP2_DEVICE_TRACE=0 traces on the host pool instead): the
 // cursor DFS (spf_trace_cursor_kernel) keeps one pathLinks cursor per node in
@@ -942,7 +954,8 @@ bool deviceTraceEnabled() {
 
 DeviceTraces traceSecondPasses(
     LinkState::Engine& eng, const std::vector<uint32_t>& sources,
-    const std::vector<uint32_t>& dests, const std::vector<std::vector<uint32_t>>& lists) {
+    const std::vector<uint32_t>& dests, const std::vector<std::vector<uint32_t>>& lists,
+    const int32_t* nodeLabels = nullptr) {
   const auto tBatch = std::chrono::steady_clock::now();
   const uint32_t V = (uint32_t)eng.names.size();
   const uint32_t nq = (uint32_t)sources.size();
@@ -960,6 +973,14 @@ DeviceTraces traceSecondPasses(
     }
     out.links.resize(nl);
     out.ends.resize(np);
+    out.cost.resize(nodeLabels ? np : 0);
+    out.labels.resize(nodeLabels ? nl - np : 0);
+  };
+  auto expandUs = [](std::chrono::steady_clock::time_point t0) {
+    Counters::add("decision.kth_expand_us",
+                  std::chrono::duration_cast<std::chrono::microseconds>(
+                      std::chrono::steady_clock::now() - t0)
+                      .count());
   };
   std::vector<uint32_t> ioff{0}, ilinks;
   for (const auto& l : lists) {
@@ -1041,6 +1062,14 @@ DeviceTraces traceSecondPasses(
                     std::chrono::duration_cast<std::chrono::microseconds>(
                         std::chrono::steady_clock::now() - tTr)
                         .count());
+      if (st == SPF_OK && nodeLabels) {
+        const auto tEx = std::chrono::steady_clock::now();
+        if ((st = spf_table_trace_expand(t, nodeLabels)) == SPF_OK) {
+          st = spf_table_trace_expand_fetch(t, out.cost.data(), out.labels.data());
+        }
+        out.expanded = st == SPF_OK;
+        expandUs(tEx);
+      }
     }
     if (st != SPF_OK) {
       engineFailure("spf_table (KSP2 device traces)", st);
@@ -1087,6 +1116,15 @@ DeviceTraces traceSecondPasses(
                   std::chrono::duration_cast<std::chrono::microseconds>(
                       std::chrono::steady_clock::now() - tTr)
                       .count());
+    if (nodeLabels) {
+      const auto tEx = std::chrono::steady_clock::now();
+      if ((s = spf_query_trace_expand(q, nodeLabels)) != SPF_OK ||
+          (s = spf_query_trace_expand_fetch(q, out.cost.data(), out.labels.data())) != SPF_OK) {
+        engineFailure("spf_query_trace_expand", s);
+      }
+      out.expanded = true;
+      expandUs(tEx);
+    }
     for (uint32_t i = 0; i < nq; ++i) {
       if (out.count[i] == SPF_TRACE_OVERFLOW) {
         auto row = std::make_shared<std::vector<uint32_t>>(V);
@@ -1289,7 +1327,8 @@ LinkState::LinkState(LinkState&& o) noexcept
       kthFill_(std::move(o.kthFill_)),
       engine_(std::move(o.engine_)),
       retired_(std::move(o.retired_)),
-      topoGen_(o.topoGen_) {}
+      topoGen_(o.topoGen_),
+      labelGen_(o.labelGen_) {}
 
 size_t LinkState::LinkPtrHash::operator()(const std::shared_ptr<Link>& l) const {
   return l->hash;
@@ -2033,6 +2072,9 @@ LinkState::LinkStateChange LinkState::updateAdjacencyDatabase(
       updateNodeOverloaded(nodeName, newDb.isOverloaded, holdUpTtl, holdDownTtl);
   change.topologyChanged |= transitChanged;
   change.nodeLabelChanged = priorDb.nodeLabel != newDb.nodeLabel;
+  if (change.nodeLabelChanged) {
+    ++labelGen_; // stored k-th path expansions carry the old label
+  }
   // what the device graph needs: a rebuild when the set of up links changes,
   // else in-place transit / metric patches
   bool structural = false;
@@ -2564,6 +2606,24 @@ const Link& LinkState::linkOfId(uint32_t id) const {
   return *engine().links.at(id);
 }
 
+const std::vector<int32_t>& LinkState::kthLabels() const {
+  static std::mutex mu;
+  std::lock_guard<std::mutex> g(mu);
+  if (kthLabelsTopo_ != topoGen_ || kthLabelsGen_ != labelGen_) {
+    const auto& eng = engine();
+    kthLabels_.assign(eng.names.size(), 0);
+    for (size_t i = 0; i < eng.names.size(); ++i) {
+      auto it = adjacencyDatabases_.find(eng.names[i]);
+      if (it != adjacencyDatabases_.end()) {
+        kthLabels_[i] = it->second.nodeLabel;
+      }
+    }
+    kthLabelsTopo_ = topoGen_;
+    kthLabelsGen_ = labelGen_;
+  }
+  return kthLabels_;
+}
+
 const LinkState::KthPathIds& LinkState::kthPathIds(
     const std::string& src, const std::string& dest, size_t k) const {
   if (k < 1) {
@@ -2753,10 +2813,12 @@ void LinkState::prefetchKthPaths(
   // k = 1 paths of every destination (independent traces over the same
   // row: host worker pool), then their links as the ignore lists
   std::vector<std::vector<uint32_t>> ignAll(todo.size());
+  std::vector<const KthPathIds*> firstIds(todo.size());
   const auto tTrace = std::chrono::steady_clock::now();
   parallelFor(todo.size(), hostThreads(todo.size(), 32), [&](size_t i, unsigned) {
     auto& ign = ignAll[i];
-    ign = kthPathIds(src, *todo[i].first, 1).links;
+    firstIds[i] = &kthPathIds(src, *todo[i].first, 1);
+    ign = firstIds[i]->links;
     std::sort(ign.begin(), ign.end());
     ign.erase(std::unique(ign.begin(), ign.end()), ign.end());
   });
@@ -2764,6 +2826,62 @@ void LinkState::prefetchKthPaths(
                 std::chrono::duration_cast<std::chrono::microseconds>(
                     std::chrono::steady_clock::now() - tTrace)
                     .count());
+  // the device expansion (opt-in): node labels by graph node id, and the
+  // k = 1 paths just traced as one spf_graph_expand_paths batch
+  const std::vector<int32_t>* nodeLabels = nullptr;
+  if (deviceExpandEnabled() && !eng.exact && eng.graph) {
+    nodeLabels = &kthLabels();
+    const auto tEx = std::chrono::steady_clock::now();
+    std::vector<size_t> firsts; // todo entries to expand
+    std::vector<uint32_t> xsrc, xoff{0}, xlinks;
+    for (size_t i = 0; i < todo.size(); ++i) {
+      const KthPathIds& ids = *firstIds[i];
+      if (ids.size() == 0 || kthExpansion(ids)) {
+        continue;
+      }
+      firsts.push_back(i);
+      xsrc.insert(xsrc.end(), ids.size(), sid->second);
+      const uint32_t base = (uint32_t)xlinks.size();
+      xlinks.insert(xlinks.end(), ids.links.begin(), ids.links.end());
+      for (size_t p = 1; p <= ids.size(); ++p) {
+        xoff.push_back(base + ids.off[p]);
+      }
+    }
+    if (!firsts.empty()) {
+      struct Block {
+        std::vector<uint64_t> cost;
+        std::vector<int32_t> labels;
+      };
+      auto blk = std::make_shared<Block>();
+      blk->cost.resize(xsrc.size());
+      blk->labels.resize(xlinks.size() - xsrc.size() + 1);
+      {
+        std::lock_guard<std::mutex> dev(eng.devMu);
+        const int st = spf_graph_expand_paths(
+            eng.graph, (uint32_t)xsrc.size(), xsrc.data(), xoff.data(), xlinks.data(),
+            nodeLabels->data(), blk->cost.data(), blk->labels.data());
+        if (st != SPF_OK) {
+          engineFailure("spf_graph_expand_paths", st);
+        }
+      }
+      size_t po = 0, lo = 0;
+      for (const size_t i : firsts) {
+        const KthPathIds& ids = *firstIds[i];
+        KthExpansion& ex = ids.expansion;
+        ex.labelGen = labelGen_;
+        ex.dest = todo[i].second;
+        ex.cost = blk->cost.data() + po;
+        ex.labels = blk->labels.data() + lo;
+        ex.keep = blk;
+        po += ids.size();
+        lo += ids.links.size() - ids.size();
+      }
+      Counters::add("decision.kth_expand_us",
+                    std::chrono::duration_cast<std::chrono::microseconds>(
+                        std::chrono::steady_clock::now() - tEx)
+                        .count());
+    }
+  }
   std::vector<uint32_t> sources;
   std::vector<uint32_t> dstIds;
   std::vector<std::vector<uint32_t>> lists;
@@ -2790,7 +2908,8 @@ void LinkState::prefetchKthPaths(
     const auto tDev = std::chrono::steady_clock::now();
     {
       std::lock_guard<std::mutex> dev(eng.devMu);
-      tr = traceSecondPasses(eng, sources, dstIds, lists);
+      tr = traceSecondPasses(eng, sources, dstIds, lists,
+                             nodeLabels ? nodeLabels->data() : nullptr);
     }
     const auto tFill = std::chrono::steady_clock::now();
     Counters::add("decision.kth_lists_us",
@@ -2822,6 +2941,17 @@ void LinkState::prefetchKthPaths(
       lo += tr.linkCount[i];
       po += tr.count[i];
     }
+    // the batch's costs and labels: one block, sliced by the entries
+    struct XBlock {
+      std::vector<uint64_t> cost;
+      std::vector<int32_t> labels;
+    };
+    std::shared_ptr<XBlock> xblk;
+    if (tr.expanded && traced) {
+      xblk = std::make_shared<XBlock>();
+      xblk->cost = std::move(tr.cost);
+      xblk->labels = std::move(tr.labels);
+    }
     std::atomic<int64_t> filled{0};
     parallelFor(kKthStripes, hostThreads(tr.count.size(), 256), [&](size_t st, unsigned) {
       KthStripe& stripe = (*kth_)[st];
@@ -2835,6 +2965,14 @@ void LinkState::prefetchKthPaths(
         paths.off.reserve(tr.count[f.i] + 1);
         for (uint32_t p = 0; p < tr.count[f.i]; ++p) {
           paths.off.push_back(E[p]);
+        }
+        if (xblk) {
+          KthExpansion& ex = paths.expansion;
+          ex.labelGen = labelGen_;
+          ex.dest = dstIds[f.i];
+          ex.cost = xblk->cost.data() + f.po;
+          ex.labels = xblk->labels.data() + (f.lo - f.po);
+          ex.keep = xblk;
         }
         n += stripe.ids.emplace(KthKey{src, *f.dst, 2}, std::move(paths)).second ? 1 : 0;
       }

@@ -332,14 +332,40 @@ class LinkState {
   // in: path i is links [begin(i), end(i)), device-graph link ids (linkOfId)
   // in path order.  Same paths in the same order, no Link refcounts touched;
   // valid until the next topology change.
+  // What selectKsp2 derives from the paths of one KthPathIds entry, computed
+  // on the device (spf_path_expand_kernel, OPENR_KSP2_DEVICE_EXPAND=1): per
+  // path the link-metric cost from the source (kInvalid = walk it on the
+  // host) and the node labels of its hops after the first in stack order;
+  // path i's labels are labels[off[i] - i .. off[i + 1] - i - 1).  Slices of
+  // one block per prefetch batch (`keep`); cost == nullptr: not expanded.
+  // Valid while the node labels are those of generation `labelGen`.
+  struct KthExpansion {
+    static constexpr uint64_t kInvalid = ~0ull; // SPF_EXPAND_INVALID
+    uint64_t labelGen{0};
+    uint32_t dest{~0u}; // the paths' last node (device-graph node id)
+    const uint64_t* cost{nullptr};
+    const int32_t* labels{nullptr};
+    std::shared_ptr<const void> keep;
+  };
   struct KthPathIds {
     std::vector<uint32_t> off{0};
     std::vector<uint32_t> links;
+    // set by prefetchKthPaths only, before the build's workers read the memo
+    mutable KthExpansion expansion;
     size_t size() const { return off.size() - 1; }
     const uint32_t* begin(size_t i) const { return links.data() + off[i]; }
     const uint32_t* end(size_t i) const { return links.data() + off[i + 1]; }
   };
   const KthPathIds& kthPathIds(const std::string& src, const std::string& dest, size_t k) const;
+  // the entry's device expansion if one is stored and its node labels are
+  // still current, else null (the caller walks the paths itself)
+  const KthExpansion* kthExpansion(const KthPathIds& ids) const {
+    const KthExpansion& ex = ids.expansion;
+    return ex.cost && ex.labelGen == labelGen_ ? &ex : nullptr;
+  }
+  // bumped whenever updateAdjacencyDatabase changes a nodeLabel: a label
+  // change keeps the topology (and the k-th path memo), not the label stacks
+  uint64_t labelGeneration() const { return labelGen_; }
   const Link& linkOfId(uint32_t id) const;
 
   // ---- MI355X engine extensions (not part of the reference API) ----
@@ -407,6 +433,11 @@ class LinkState {
   // bumped on every topology change (clearMemo / patchMemo): flat views of an
   // older generation are stale
   mutable uint64_t topoGen_{0};
+  uint64_t labelGen_{0};
+  // nodeLabel by device-graph node id, of (topoGen_, labelGen_) (kthLabels)
+  mutable std::vector<int32_t> kthLabels_;
+  mutable uint64_t kthLabelsTopo_{~0ull}, kthLabelsGen_{~0ull};
+  const std::vector<int32_t>& kthLabels() const;
   void patchMemo(
       const std::vector<std::string>& transitNodes,
       const std::vector<std::pair<std::shared_ptr<Link>, std::string>>& metricPatches) const;

@@ -223,7 +223,12 @@ struct EcmpClock {
   // ECMP: best nodes, next-hop nodes, thrift, insert; KSP2: best nodes,
   // paths (k = 1, 2), next hops + label stacks, rest
   int64_t ns[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t deviceExpanded = 0; // KSP2 next hops built from a device expansion
   void flush() {
+    if (deviceExpanded) {
+      Counters::add("decision.ksp2_device_expanded", deviceExpanded);
+      deviceExpanded = 0;
+    }
     static const char* kKeys[8] = {
         "decision.ecmp_best_us", "decision.ecmp_nhnodes_us", "decision.ecmp_thrift_us",
         "decision.ecmp_insert_us", "decision.ksp2_best_us", "decision.ksp2_paths_us",
@@ -1495,9 +1500,24 @@ void SpfSolver::SpfSolverImpl::selectKsp2(
     const LinkState* ls;
     const uint32_t* first;
     const uint32_t* last;
+    // the path's device expansion (LinkState::KthExpansion), if a current
+    // one is stored: cost, and its label span [labels, labels + size() - 1)
+    const uint64_t* cost = nullptr;
+    const int32_t* labels = nullptr;
+    uint32_t dest = ~0u; // destination's node id (expanded paths only)
     size_t size() const { return (size_t)(last - first); }
   };
   std::vector<PathRef> paths;
+  auto pathRef = [](const LinkState& ls, const LinkState::KthPathIds& ids, size_t i,
+                    const LinkState::KthExpansion* ex) {
+    PathRef r{&ls, ids.begin(i), ids.end(i)};
+    if (ex) {
+      r.cost = ex->cost + i;
+      r.labels = ex->labels + (ids.off[i] - i);
+      r.dest = ex->dest;
+    }
+    return r;
+  };
   // LinkState::pathAInPathB on link ids: links of one area are equal iff
   // their ids are; links of different areas compare by value
   auto sameLink = [](const PathRef& a, uint32_t la, const PathRef& b, uint32_t lb) {
@@ -1526,8 +1546,9 @@ void SpfSolver::SpfSolverImpl::selectKsp2(
         continue;
       }
       const auto& first = ls.kthPathIds(myNodeName, node, 1);
+      const auto* ex = ls.kthExpansion(first);
       for (size_t i = 0; i < first.size(); ++i) {
-        paths.push_back({&ls, first.begin(i), first.end(i)});
+        paths.push_back(pathRef(ls, first, i, ex));
       }
     }
     if (algo == thrift::PrefixForwardingAlgorithm::KSP2_ED_ECMP) {
@@ -1535,8 +1556,9 @@ void SpfSolver::SpfSolverImpl::selectKsp2(
       const size_t firstPaths = paths.size();
       for (const auto& node : best.nodes) {
         const auto& second = ls.kthPathIds(myNodeName, node, 2);
+        const auto* ex = ls.kthExpansion(second);
         for (size_t j = 0; j < second.size(); ++j) {
-          const PathRef sec{&ls, second.begin(j), second.end(j)};
+          const PathRef sec = pathRef(ls, second, j, ex);
           bool contained = false;
           for (size_t i = 0; i < firstPaths && !contained; ++i) {
             contained = aInB(paths[i], sec);
@@ -1566,6 +1588,7 @@ void SpfSolver::SpfSolverImpl::selectKsp2(
   // one next hop per path and area at most: no rehash while they go in
   entry.nexthops.reserve(paths.size() * areaLinkStates.size());
   std::vector<std::pair<uint32_t, const thrift::PrefixEntry*>> destCache;
+  int64_t deviceExpanded = 0; // next hops built from a device expansion
   for (const auto& path : paths) {
     if (path.size() == 0) {
       throw std::logic_error("selectKsp2: empty path");
@@ -1577,7 +1600,15 @@ void SpfSolver::SpfSolverImpl::selectKsp2(
       uint32_t at = ksp2Fast_.me;
       hopLabels.clear();
       bool ok = true;
-      for (const uint32_t* l = path.first; l != path.last && ok; ++l) {
+      // cost and label span from the device expansion; an invalid path
+      // (KthExpansion::kInvalid) takes the walk
+      const bool expanded = path.cost && *path.cost != LinkState::KthExpansion::kInvalid;
+      if (expanded) {
+        cost = (Metric)*path.cost;
+        at = path.dest;
+        ++deviceExpanded;
+      }
+      for (const uint32_t* l = path.first; !expanded && l != path.last && ok; ++l) {
         uint32_t to = 0;
         LinkStateMetric w = 0;
         ok = path.ls->linkHop(*l, at, to, w);
@@ -1597,9 +1628,12 @@ void SpfSolver::SpfSolverImpl::selectKsp2(
           destCache.emplace_back(at, destEntry);
         }
         std::vector<int32_t> labels;
-        labels.reserve(hopLabels.size());
+        labels.reserve(path.size());
         if (destEntry->prependLabel) {
           labels.push_back(*destEntry->prependLabel); // bottom of stack
+        }
+        if (expanded) {
+          labels.insert(labels.end(), path.labels, path.labels + (path.size() - 1));
         }
         for (size_t h = hopLabels.size(); h-- > 1;) {
           labels.push_back(hopLabels[h]);
@@ -1647,6 +1681,7 @@ void SpfSolver::SpfSolverImpl::selectKsp2(
           firstLink.getArea()));
     }
   }
+  clk.deviceExpanded += deviceExpanded; // flushed once per route shard
 
   lap(6);
   int staticNexthops = 0;

@@ -284,6 +284,33 @@ PYBIND11_MODULE(_openr_spf, m) {
             }
             return out;
           })
+      .def(
+          "getKthPathExpansion",
+          // [(cost, [labels])] per path of getKthPaths(s, d, k) from the stored
+          // device expansion (cost None: an invalid path), or None when no
+          // expansion of the current node labels is stored
+          [](const LinkState& ls, const std::string& s, const std::string& d,
+             size_t k) -> py::object {
+            const auto& ids = ls.kthPathIds(s, d, k);
+            const auto* ex = ls.kthExpansion(ids);
+            if (!ex) {
+              return py::none();
+            }
+            py::list out;
+            for (size_t i = 0; i < ids.size(); ++i) {
+              py::list labels;
+              const size_t lo = ids.off[i] - i, n = ids.off[i + 1] - ids.off[i] - 1;
+              for (size_t h = 0; h < n; ++h) {
+                labels.append(ex->labels[lo + h]);
+              }
+              py::object cost = py::none();
+              if (ex->cost[i] != LinkState::KthExpansion::kInvalid) {
+                cost = py::int_(ex->cost[i]);
+              }
+              out.append(py::make_tuple(cost, labels));
+            }
+            return out;
+          })
       .def("getMetricFromAToB", &LinkState::getMetricFromAToB, py::arg("a"), py::arg("b"),
            py::arg("useLinkMetric") = true)
       .def("getHopsFromAToB", &LinkState::getHopsFromAToB)

@@ -776,6 +776,80 @@ int spf_table_trace_fetch(spf_table* t, uint32_t* links, uint32_t* ends) {
   return SPF_OK;
 }
 
+int spf_table_trace_expand(spf_table* t, const int32_t* node_labels) {
+  SPF_ABI_RANGE_CLUSTER("spf_table_trace_expand");
+  if (!t || !node_labels) {
+    return cfail(SPF_E_INVALID, "spf_table_trace_expand: null argument");
+  }
+  if (!t->traced) {
+    return cfail(SPF_E_INVALID, "spf_table_trace_expand: no trace since the last run");
+  }
+  std::vector<int> st(t->local.size(), SPF_OK);
+  std::vector<std::string> why(t->local.size());
+  std::vector<std::thread> th;
+  for (size_t j = 0; j < t->local.size(); ++j) {
+    if (!t->local[j].q) {
+      continue;
+    }
+    th.emplace_back([&, j] {
+      if (hipSetDevice(t->local[j].device) != hipSuccess) {
+        st[j] = SPF_E_DEVICE;
+        return;
+      }
+      st[j] = spf_query_trace_expand(t->local[j].q, node_labels);
+      if (st[j] != SPF_OK) {
+        why[j] = spf_last_error_detail();
+      }
+    });
+  }
+  for (auto& x : th) {
+    x.join();
+  }
+  for (size_t j = 0; j < st.size(); ++j) {
+    if (st[j] != SPF_OK) {
+      return cfail(st[j], "spf_table_trace_expand: " + why[j]);
+    }
+  }
+  return SPF_OK;
+}
+
+int spf_table_trace_expand_fetch(spf_table* t, uint64_t* cost, int32_t* labels) {
+  SPF_ABI_RANGE_CLUSTER("spf_table_trace_expand_fetch");
+  if (!t || !t->traced) {
+    return cfail(SPF_E_INVALID, "spf_table_trace_expand_fetch: no expansion to fetch");
+  }
+  std::vector<int> st(t->local.size(), SPF_OK);
+  std::vector<std::string> why(t->local.size());
+  std::vector<std::thread> th;
+  for (size_t j = 0; j < t->local.size(); ++j) {
+    if (!t->local[j].q) {
+      continue;
+    }
+    th.emplace_back([&, j] {
+      if (hipSetDevice(t->local[j].device) != hipSuccess) {
+        st[j] = SPF_E_DEVICE;
+        return;
+      }
+      // a block's labels: its links less one per path before it
+      const uint64_t pb = t->trace_path_base[j], lb = t->trace_link_base[j] - pb;
+      st[j] = spf_query_trace_expand_fetch(t->local[j].q, cost ? cost + pb : nullptr,
+                                           labels ? labels + lb : nullptr);
+      if (st[j] != SPF_OK) {
+        why[j] = spf_last_error_detail();
+      }
+    });
+  }
+  for (auto& x : th) {
+    x.join();
+  }
+  for (size_t j = 0; j < st.size(); ++j) {
+    if (st[j] != SPF_OK) {
+      return cfail(st[j], "spf_table_trace_expand_fetch: " + why[j]);
+    }
+  }
+  return SPF_OK;
+}
+
 int spf_table_fetch_nexthops(spf_table* t, uint32_t first, uint32_t count, uint64_t* dst) {
   SPF_ABI_RANGE_CLUSTER("spf_table_fetch_nexthops");
   if (!t || !dst || first + (uint64_t)count > t->n || !(t->flags & SPF_F_NEXTHOPS)) {

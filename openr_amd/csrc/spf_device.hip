@@ -8079,6 +8079,107 @@ __global__ __launch_bounds__(64) void spf_trace_pack_kernel(TracePackArgs a) {
   }
 }
 
+// selectKsp2's walk over the traced paths (Decision.cpp:970-1011): per path
+// the sum of the directional link metrics from the source, and the node
+// labels of the hops after the first in PUSH-stack order (destination first).
+struct PathExpandArgs {
+  // trace mode (out_n != nullptr): one wave per query over the trace scratch
+  // [nq][cap]; packed mode: one lane per path i, links[off[i] .. off[i + 1])
+  const uint32_t* out_n;
+  const uint32_t* out_len;   // trace: [nq] links of the query's paths
+  const uint32_t* links;
+  const uint32_t* ends;      // trace: [nq][cap] end offsets; packed: off [np + 1]
+  const uint32_t* src;       // trace: [nq] query sources; packed: [np] path sources
+  const uint32_t* off_cost;  // trace: [nq] first cost slot of the query
+  const uint32_t* off_lab;   // trace: [nq] label base of the query; packed: [np] per path
+  const uint32_t* link_half; // [2L]
+  const uint32_t* col;
+  const uint64_t* w64;
+  const int32_t* node_label; // [V]
+  uint64_t* cost;
+  int32_t* lab;
+  uint32_t cap, n, L;
+};
+
+constexpr uint32_t kPxWaves = 4;
+constexpr uint64_t kExpandInvalid = ~0ull;
+
+// one path: `len` links from node `at`; len - 1 labels at lab[0 .. len - 1)
+__device__ __forceinline__ uint64_t expand_one_path(
+    const PathExpandArgs& a, const uint32_t* links, uint32_t len, uint32_t at, int32_t* lab) {
+  uint64_t cost = 0;
+  bool ok = len != 0;
+  for (uint32_t h = 0; h < len && ok; ++h) {
+    const uint32_t l = links[h];
+    ok = l < a.L;
+    if (!ok) {
+      break;
+    }
+    const uint32_t e0 = a.link_half[2 * (size_t)l], e1 = a.link_half[2 * (size_t)l + 1];
+    ok = e0 != kInf32 && e1 != kInf32;
+    if (!ok) {
+      break;
+    }
+    // LinkState::linkHop: half e0 runs col[e1] -> col[e0]
+    const uint32_t first = a.col[e1], second = a.col[e0];
+    uint32_t e;
+    if (at == first) {
+      e = e0;
+      at = second;
+    } else if (at == second) {
+      e = e1;
+      at = first;
+    } else {
+      ok = false;
+      break;
+    }
+    cost += a.w64[e];
+    if (h) {
+      lab[len - 1 - h] = a.node_label[at];
+    }
+  }
+  if (!ok) {
+    for (uint32_t h = 1; h < len; ++h) {
+      lab[h - 1] = 0;
+    }
+    return kExpandInvalid;
+  }
+  return cost;
+}
+
+__global__ __launch_bounds__(64 * kPxWaves) void spf_path_expand_kernel(PathExpandArgs a) {
+  if (!a.out_n) {
+    const uint32_t i = blockIdx.x * (64 * kPxWaves) + threadIdx.x;
+    if (i < a.n) {
+      const uint32_t b = a.ends[i];
+      a.cost[i] = expand_one_path(a, a.links + b, a.ends[i + 1] - b, a.src[i], a.lab + a.off_lab[i]);
+    }
+    return;
+  }
+  const uint32_t q = blockIdx.x * kPxWaves + (threadIdx.x >> 6);
+  if (q >= a.n) {
+    return;
+  }
+  const uint32_t np = a.out_n[q];
+  if (np == kTraceOverflow) {
+    return;
+  }
+  const uint32_t* links = a.links + (size_t)q * a.cap;
+  const uint32_t* ends = a.ends + (size_t)q * a.cap;
+  const uint32_t at = a.src[q];
+  const uint32_t nl = min(a.out_len[q], a.cap);
+  for (uint32_t p = threadIdx.x & 63u; p < np && p < a.cap; p += 64) {
+    const uint32_t b = p ? ends[p - 1] : 0u, e = ends[p];
+    // path p's labels start at (its first link) - p: every earlier path of
+    // the query dropped one; a malformed row (empty path, ends not ascending
+    // or past the query's links) writes no label
+    const bool sane = b < e && b >= p && (uint64_t)e + (np - 1 - p) <= nl;
+    a.cost[a.off_cost[q] + p] =
+        sane ? expand_one_path(a, links + b, e - b, at, a.lab + a.off_lab[q] + (b - p))
+             : kExpandInvalid;
+  }
+}
+
 constexpr int kPatch32 = 6; // wout, win, nbr_w, cw, col, sell (u32 words)
 struct PatchArgs {
   const uint32_t* pk;   // (index, value) pairs per u32 array, then (index, lo, hi)
@@ -8332,6 +8433,17 @@ struct spf_query {
   uint32_t trace_n = 0, trace_cap = 0;
   uint64_t trace_links = 0, trace_paths = 0;
   std::vector<uint32_t> trace_pc, trace_lc;
+  // the last trace's query range start and the run it read (an expansion
+  // needs the rows' sources and a trace newer than the last run)
+  uint32_t trace_first = 0;
+  uint64_t trace_run = 0;
+  bool trace_valid = false;
+  // spf_query_trace_expand: cost [paths] u64 | labels | node labels [V] |
+  // per-query offsets [2 * trace_n] (one pooled block), kept until the fetch
+  char* d_expand = nullptr;
+  size_t expand_bytes = 0;
+  uint64_t expand_costs = 0, expand_labels = 0;
+  bool expanded = false;
   void* d_pack = nullptr;     // the batch's index arrays (one pooled block)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t evm = nullptr; // after the distance stage, before next hops
@@ -9053,7 +9165,7 @@ void free_query(spf_query* q) {
         (void*)q->d_ovf, q->narrow ? (void*)q->d_nhb : nullptr, (void*)q->d_tcs, q->d_v2,
         (void*)q->d_trit,
         q->d_coop, (void*)q->d_wh_cand, (void*)q->d_wh_mark, (void*)q->d_wh_lstart,
-        (void*)q->d_fh, (void*)q->d_ms_blocked}) {
+        (void*)q->d_fh, (void*)q->d_ms_blocked, (void*)q->d_expand}) {
     pool_free(p);
   }
   if (q->base) {
@@ -12881,7 +12993,12 @@ int spf_query_trace_paths(
   q->trace_n = 0;
   q->trace_links = 0;
   q->trace_paths = 0;
+  q->trace_first = first;
+  q->trace_run = q->runs;
+  q->trace_valid = false;
+  q->expanded = false;
   if (count == 0) {
+    q->trace_valid = true;
     return SPF_OK;
   }
   HIP_TRY(hipSetDevice(g->device));
@@ -13143,6 +13260,7 @@ int spf_query_trace_paths(
     }
   }
   q->trace_n = count;
+  q->trace_valid = true;
   q->trace_pc.assign(path_count, path_count + count);
   q->trace_lc.assign(link_count, link_count + count);
   for (uint32_t i = 0; i < count; ++i) {
@@ -13207,6 +13325,229 @@ int spf_query_trace_fetch(spf_query* q, uint32_t* links, uint32_t* ends) {
   }
   if (po) {
     HIP_TRY(hipMemcpyAsync(ends, a.dst_ends, po * 4, hipMemcpyDeviceToHost, g->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  return SPF_OK;
+}
+
+namespace {
+
+// the graph side of spf_path_expand_kernel's arguments
+int expand_graph_args(const spf_graph* g, PathExpandArgs& a) {
+  if (g->links_patched) {
+    // half-edges taken down in place are self-loops of their tail: a walk
+    // over them would not be the link's
+    return fail(SPF_E_UNSUPPORTED, "path expansion on a graph patched by spf_graph_set_edges");
+  }
+  a.link_half = g->d_link_half;
+  a.col = g->d_col;
+  a.w64 = g->d_w64;
+  a.L = g->E ? g->L : 0; // no half-edge: every link id is invalid
+  return SPF_OK;
+}
+
+} // namespace
+
+int spf_query_trace_expand(spf_query* q, const int32_t* node_labels) {
+  SPF_ABI_RANGE("spf_query_trace_expand");
+  if (!q || !node_labels) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  if (!q->ran) {
+    return fail(SPF_E_INVALID, "query has not run");
+  }
+  if (rows64(q)) {
+    return fail(SPF_E_UNSUPPORTED, "64-bit distance rows (settle keys): trace on the host");
+  }
+  if (!q->trace_valid || q->trace_run != q->runs) {
+    return fail(SPF_E_INVALID, "no trace since the last run");
+  }
+  spf_graph* g = q->g;
+  PathExpandArgs a{};
+  if (const int st = expand_graph_args(g, a)) {
+    return st;
+  }
+  q->expanded = false;
+  q->expand_costs = 0;
+  q->expand_labels = 0;
+  const uint32_t count = q->trace_n;
+  if (count == 0 || q->trace_paths == 0) {
+    q->expanded = true;
+    return SPF_OK;
+  }
+  HIP_TRY(hipSetDevice(g->device));
+  // per-query cost and label bases (host scan, as spf_query_trace_fetch)
+  std::vector<uint32_t> off(2 * (size_t)count);
+  uint64_t po = 0, lo = 0;
+  for (uint32_t i = 0; i < count; ++i) {
+    const bool ok = q->trace_pc[i] != SPF_TRACE_OVERFLOW && q->trace_lc[i] >= q->trace_pc[i];
+    off[i] = (uint32_t)po;
+    off[count + i] = (uint32_t)lo;
+    po += ok ? q->trace_pc[i] : 0;
+    lo += ok ? q->trace_lc[i] - q->trace_pc[i] : 0;
+  }
+  if (po != q->trace_paths || po > 0xFFFFFFFFull || lo > 0xFFFFFFFFull) {
+    return fail(SPF_E_INVALID, "trace counts out of range");
+  }
+  const size_t o_lab = (size_t)po * 8;
+  const size_t o_nl = o_lab + (size_t)lo * 4;
+  const size_t o_off = o_nl + (size_t)g->V * 4;
+  const size_t need = o_off + off.size() * 4;
+  if (q->d_expand && q->expand_bytes < need) {
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    pool_free(q->d_expand);
+    q->d_expand = nullptr;
+  }
+  if (!q->d_expand) {
+    HIP_TRY(pool_malloc((void**)&q->d_expand, need));
+    q->expand_bytes = need;
+  }
+  char* buf = q->d_expand;
+  HIP_TRY(hipMemcpyAsync(buf + o_nl, node_labels, (size_t)g->V * 4, hipMemcpyHostToDevice,
+                         g->stream));
+  HIP_TRY(hipMemcpyAsync(buf + o_off, off.data(), off.size() * 4, hipMemcpyHostToDevice,
+                         g->stream));
+  const size_t cells = (size_t)count * q->trace_cap;
+  const uint32_t* tr = q->d_trace;
+  a.out_n = tr + count;
+  a.out_len = tr + 2 * (size_t)count;
+  a.links = tr + 3 * (size_t)count;
+  a.ends = tr + 3 * (size_t)count + cells;
+  a.src = q->d_src + q->trace_first;
+  a.off_cost = reinterpret_cast<const uint32_t*>(buf + o_off);
+  a.off_lab = a.off_cost + count;
+  a.node_label = reinterpret_cast<const int32_t*>(buf + o_nl);
+  a.cost = reinterpret_cast<uint64_t*>(buf);
+  a.lab = reinterpret_cast<int32_t*>(buf + o_lab);
+  a.cap = q->trace_cap;
+  a.n = count;
+  {
+    // the kernel joins the run's launch list (spf_query_kernels)
+    const bool own = !tl_launched;
+    if (own) {
+      tl_launched = &q->launched;
+    }
+    SPF_LAUNCH(spf_path_expand_kernel, dim3((count + kPxWaves - 1) / kPxWaves),
+               dim3(64 * kPxWaves), 0, g->stream, a);
+    if (own) {
+      tl_launched = nullptr;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  q->expand_costs = po;
+  q->expand_labels = lo;
+  q->expanded = true;
+  return SPF_OK;
+}
+
+int spf_query_trace_expand_fetch(spf_query* q, uint64_t* cost, int32_t* labels) {
+  SPF_ABI_RANGE("spf_query_trace_expand_fetch");
+  if (!q) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  if (!q->expanded || !q->trace_valid || q->trace_run != q->runs) {
+    return fail(SPF_E_INVALID, "no expansion to fetch");
+  }
+  if ((q->expand_costs && !cost) || (q->expand_labels && !labels)) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  if (q->expand_costs == 0) {
+    return SPF_OK;
+  }
+  spf_graph* g = q->g;
+  HIP_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipMemcpyAsync(cost, q->d_expand, q->expand_costs * 8, hipMemcpyDeviceToHost,
+                         g->stream));
+  if (q->expand_labels) {
+    HIP_TRY(hipMemcpyAsync(labels, q->d_expand + q->expand_costs * 8, q->expand_labels * 4,
+                           hipMemcpyDeviceToHost, g->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  return SPF_OK;
+}
+
+int spf_graph_expand_paths(
+    spf_graph* g, uint32_t num_paths, const uint32_t* sources, const uint32_t* off,
+    const uint32_t* links, const int32_t* node_labels, uint64_t* cost, int32_t* labels) {
+  SPF_ABI_RANGE("spf_graph_expand_paths");
+  if (!g || !node_labels || (num_paths && (!sources || !off || !cost))) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  if (num_paths == 0) {
+    return SPF_OK;
+  }
+  // label slot of every path: Σ max(len - 1, 0) before it (off[i] - i while
+  // no path is empty)
+  std::vector<uint32_t> lab_off(num_paths);
+  uint64_t lo = 0;
+  for (uint32_t i = 0; i < num_paths; ++i) {
+    if (sources[i] >= g->V) {
+      return fail(SPF_E_INVALID, "source out of range");
+    }
+    if (off[i + 1] < off[i]) {
+      return fail(SPF_E_INVALID, "path offsets not ascending");
+    }
+    lab_off[i] = (uint32_t)lo;
+    const uint32_t len = off[i + 1] - off[i];
+    lo += len ? len - 1 : 0;
+  }
+  const uint32_t nl = off[num_paths] - off[0];
+  if ((nl && !links) || (lo && !labels)) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  PathExpandArgs a{};
+  if (const int st = expand_graph_args(g, a)) {
+    return st;
+  }
+  HIP_TRY(hipSetDevice(g->device));
+  // cost [np] u64 | labels [lo] | node labels [V] | sources [np] | off [np + 1]
+  // (rebased to 0) | label slots [np] | links [nl]
+  const size_t np = num_paths;
+  const size_t o_lab = np * 8;
+  const size_t o_nl = o_lab + (size_t)lo * 4;
+  const size_t o_src = o_nl + (size_t)g->V * 4;
+  const size_t o_off = o_src + np * 4;
+  const size_t o_slot = o_off + (np + 1) * 4;
+  const size_t o_links = o_slot + np * 4;
+  char* buf = nullptr;
+  HIP_TRY(pool_malloc((void**)&buf, o_links + (size_t)std::max<uint32_t>(nl, 1) * 4));
+  struct Free {
+    char* p;
+    hipStream_t st;
+    ~Free() {
+      (void)hipStreamSynchronize(st);
+      pool_free(p);
+    }
+  } guard{buf, g->stream};
+  std::vector<uint32_t> roff(off, off + np + 1);
+  for (auto& x : roff) {
+    x -= off[0];
+  }
+  HIP_TRY(hipMemcpyAsync(buf + o_nl, node_labels, (size_t)g->V * 4, hipMemcpyHostToDevice,
+                         g->stream));
+  HIP_TRY(hipMemcpyAsync(buf + o_src, sources, np * 4, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemcpyAsync(buf + o_off, roff.data(), (np + 1) * 4, hipMemcpyHostToDevice,
+                         g->stream));
+  HIP_TRY(hipMemcpyAsync(buf + o_slot, lab_off.data(), np * 4, hipMemcpyHostToDevice,
+                         g->stream));
+  if (nl) {
+    HIP_TRY(hipMemcpyAsync(buf + o_links, links + off[0], (size_t)nl * 4, hipMemcpyHostToDevice,
+                           g->stream));
+  }
+  a.links = reinterpret_cast<const uint32_t*>(buf + o_links);
+  a.ends = reinterpret_cast<const uint32_t*>(buf + o_off);
+  a.src = reinterpret_cast<const uint32_t*>(buf + o_src);
+  a.off_lab = reinterpret_cast<const uint32_t*>(buf + o_slot);
+  a.node_label = reinterpret_cast<const int32_t*>(buf + o_nl);
+  a.cost = reinterpret_cast<uint64_t*>(buf);
+  a.lab = reinterpret_cast<int32_t*>(buf + o_lab);
+  a.n = num_paths;
+  SPF_LAUNCH(spf_path_expand_kernel, dim3((num_paths + 64 * kPxWaves - 1) / (64 * kPxWaves)),
+             dim3(64 * kPxWaves), 0, g->stream, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(cost, buf, np * 8, hipMemcpyDeviceToHost, g->stream));
+  if (lo) {
+    HIP_TRY(hipMemcpyAsync(labels, buf + o_lab, (size_t)lo * 4, hipMemcpyDeviceToHost, g->stream));
   }
   HIP_TRY(hipStreamSynchronize(g->stream));
   return SPF_OK;
