@@ -237,6 +237,19 @@ int spf_query_fetch_rows(
     int dst_on_device);
 /* Elements between consecutive distance rows (>= V). */
 uint32_t spf_query_row_stride(const spf_query* q);
+/* The batch's 8-bit level rows into a level slot of a SPF_T_GATHER_LEVELS
+ * table (below), after a run, asynchronously on the graph stream: on the
+ * MS-BFS plan (uniform metric or SPF_F_UNIT_METRIC, many sources) query i's
+ * row holds one byte per node, distance = level * scale, 255 = not reached,
+ * exact while no level of the run reached 255.  Rows [0, num_queries) are
+ * copied to dst_dev, dst_pitch (>= V) bytes apart, and a small kernel writes
+ * the 16-byte trailer at trailer_dev: four uint32 words, [0] flags (bit 0
+ * "deep": a level >= 255 occurred in THIS run; bit 1: the query has no level
+ * rows -- another plan, the zero-metric variant plan, 64-bit rows, a what-if
+ * batch behind a screen -- and nothing but the trailer is written), [1]
+ * scale, [2] the row count, [3] 0.  Both pointers are device memory of the
+ * graph's device. */
+int spf_query_pack_levels(spf_query* q, void* dst_dev, size_t dst_pitch, void* trailer_dev);
 /* Copy the next-hop masks of queries [first, first+count) to host memory in
  * one transfer, back to back: query i occupies V * nh_words(i) words.  The
  * bulk counterpart of spf_query_nexthops for batches whose every row the
@@ -457,6 +470,34 @@ typedef struct spf_table spf_table;
 #define SPF_CLUSTER_ID_BYTES 128
 #define SPF_T_GATHER_ROWS 0x100u     /* all-gather the uint32 distance rows */
 #define SPF_T_GATHER_NEXTHOPS 0x200u /* all-gather the packed next-hop masks */
+/* All-gather the distance rows as 8-bit LEVEL rows, a quarter of the uint32
+ * bytes: on a uniform metric (or SPF_F_UNIT_METRIC) the MS-BFS plan's level
+ * byte encodes a distance exactly (distance = level * scale, 255 = not
+ * reached) while no level reaches 255.  Allowed with SPF_T_GATHER_NEXTHOPS;
+ * with SPF_T_GATHER_ROWS it is SPF_E_INVALID.  Creation refuses it with
+ * SPF_E_UNSUPPORTED only for facts of the graph, equal on every rank, that
+ * rule the MS-BFS plan out for good (a metric that is not uniform without
+ * SPF_F_UNIT_METRIC, more nodes than the plan holds); what depends on a
+ * rank's block or on a run is decided per run:
+ *   - spf_table_run copies each local block's level rows into its slot
+ *     (spf_query_pack_levels; layout: spf_table_levels_layout) and exchanges
+ *     the slots with ONE in-place all-gather of slot_bytes bytes; no uint32
+ *     row is copied or exchanged.
+ *   - The run is RESOLVED in spf_table_sync (and implicitly by any reader of
+ *     gathered data, and by spf_table_row_form / spf_table_elapsed_ms, when
+ *     the last run is unresolved): the `world` trailers are read from one
+ *     local device.  All flags words 0: the run's form is LEVELS.  Otherwise
+ *     (a deep BFS, or a block without level rows) it is ROWS32, the fallback:
+ *     the uint32 gathered buffer is allocated (once), each block's rows are
+ *     copied into its slot and all-gathered exactly as SPF_T_GATHER_ROWS
+ *     does.  Every rank reads the same trailers and so takes the same branch,
+ *     but the fallback is a collective: for such a table spf_table_sync (and
+ *     the first reader after a run) is COLLECTIVE -- every rank must call it
+ *     after every run.  The form is decided anew on every run (a drain can
+ *     make a BFS deep or shallow again).  A block on a 64-bit plan fails
+ *     the fallback with SPF_E_UNSUPPORTED, as a SPF_T_GATHER_ROWS run does.
+ *   - Readers return the same uint32 rows in either form. */
+#define SPF_T_GATHER_LEVELS 0x400u
 
 int spf_cluster_unique_id(uint8_t* id /*[SPF_CLUSTER_ID_BYTES]*/);
 int spf_cluster_create_local(uint32_t num_devices, const int* devices, spf_cluster** out);
@@ -476,18 +517,35 @@ const char* spf_cluster_last_error(void);
 int spf_table_layout(
     uint32_t num_sources, uint32_t world, uint32_t num_nodes, const uint32_t* nh_bytes,
     uint64_t* block_first, uint64_t* mask_off, uint64_t* mask_cap);
+/* Host only: the level slots of a SPF_T_GATHER_LEVELS table.  Each of the
+ * `world` equal slots of *slot_bytes bytes (a multiple of 16) holds cap =
+ * ceil(num_sources / world) level rows *pitch bytes apart (*pitch = num_nodes
+ * rounded up to 16, the level-row stride of a query, so a block's rows are
+ * one contiguous run; the bytes [num_nodes, pitch) of a row are padding) and,
+ * *trailer_off = cap * pitch bytes into the slot, the block's 16-byte trailer
+ * (spf_query_pack_levels; all zero for a rank with an empty block).  Source i
+ * of rank r's block (spf_table_layout's block_first) is at r * slot_bytes +
+ * (i - block_first[r]) * pitch.  Any output pointer may be NULL, not all. */
+int spf_table_levels_layout(
+    uint32_t num_sources, uint32_t world, uint32_t num_nodes, uint64_t* pitch,
+    uint64_t* slot_bytes, uint64_t* trailer_off);
 /* One graph per local device from `desc` (desc->device ignored), the local
  * ranks' source blocks as queries.  flags: SPF_F_UNIT_METRIC,
- * SPF_F_NEXTHOPS, SPF_T_GATHER_ROWS, SPF_T_GATHER_NEXTHOPS. */
+ * SPF_F_NEXTHOPS, SPF_T_GATHER_ROWS, SPF_T_GATHER_NEXTHOPS,
+ * SPF_T_GATHER_LEVELS. */
 int spf_table_create(
     spf_cluster* c, const spf_graph_desc* desc, uint32_t num_sources, const uint32_t* sources,
     uint32_t flags, spf_table** out);
 int spf_table_destroy(spf_table* t);
 /* Enqueue every local block and the all-gathers (asynchronous). */
 int spf_table_run(spf_table* t);
+/* Wait for the last run (and for spf_table_expand_rows calls since).  For a
+ * SPF_T_GATHER_LEVELS table it also resolves the run's form and is
+ * COLLECTIVE (see the flag). */
 int spf_table_sync(spf_table* t);
 /* Device time of the last run, max over local devices: the SPF batch (plus
- * the copy into the own slot) and the RCCL exchange. */
+ * the copy into the own slot) and the RCCL exchange (a SPF_T_GATHER_LEVELS
+ * run's fallback exchange included). */
 int spf_table_elapsed_ms(spf_table* t, float* compute_ms, float* gather_ms);
 int spf_table_block(const spf_table* t, uint32_t rank, uint32_t* first, uint32_t* count);
 int spf_table_nh_words(const spf_table* t, uint32_t i);
@@ -495,10 +553,42 @@ int spf_table_nh_words(const spf_table* t, uint32_t i);
 int spf_table_nh_bytes(const spf_table* t, uint32_t i);
 /* Rows / masks of sources [first, first+count) to host memory (from the
  * local owner, or from the gathered copy; SPF_E_UNSUPPORTED for another
- * rank's rows without the gather flag).  Masks back to back, V * nh_words(i)
+ * rank's rows without the gather flag).  With SPF_T_GATHER_LEVELS another
+ * rank's rows are expanded on the device (spf_table_expand_rows' routine, a
+ * bounded scratch) and copied from there.  Masks back to back, V * nh_words(i)
  * words each. */
 int spf_table_fetch_rows(spf_table* t, uint32_t first, uint32_t count, uint32_t* dst);
 int spf_table_fetch_nexthops(spf_table* t, uint32_t first, uint32_t count, uint64_t* dst);
+/* SPF_T_GATHER_LEVELS readers (all resolve an unresolved run first).
+ * spf_table_row_form: *form = SPF_ROW_FORM_* of the last run (a table without
+ * the flag: ROWS32 with SPF_T_GATHER_ROWS, else NONE), *scale = the level
+ * scale (LEVELS form, else 0), *gathered_bytes = the bytes each rank received
+ * in the last run's row exchange (LEVELS: world * slot_bytes; the fallback
+ * adds world * cap * V * 4).  Outputs may be NULL. */
+#define SPF_ROW_FORM_NONE 0u
+#define SPF_ROW_FORM_ROWS32 1u
+#define SPF_ROW_FORM_LEVELS 2u
+int spf_table_row_form(spf_table* t, uint32_t* form, uint32_t* scale, uint64_t* gathered_bytes);
+/* The uint32 rows of sources [first, first+count) into device memory of
+ * local device `local` (dst_pitch >= 4 * V bytes apart, dst and dst_pitch
+ * multiples of 4; V entries written per row, nothing else), FROM THE GATHERED
+ * BUFFER of that device, whoever owns the sources: spf_levels_expand_kernel
+ * in LEVELS form, a strided copy in ROWS32 form (also a SPF_T_GATHER_ROWS
+ * table's).  Asynchronous on that device's graph stream; spf_table_sync
+ * waits for it.  SPF_E_UNSUPPORTED for a table without a row gather. */
+int spf_table_expand_rows(
+    spf_table* t, uint32_t local, uint32_t first, uint32_t count, void* dst_dev,
+    size_t dst_pitch);
+/* The raw level bytes of sources [first, first+count) from the gathered
+ * buffer to host memory, [count][V]; SPF_E_UNSUPPORTED unless the last run's
+ * form is LEVELS. */
+int spf_table_fetch_levels(spf_table* t, uint32_t first, uint32_t count, uint8_t* dst);
+/* The gathered level slots on local device `local` ([world * slot_bytes]
+ * bytes, spf_table_levels_layout; NULL without SPF_T_GATHER_LEVELS), valid
+ * data only after a run whose form is LEVELS.  Like
+ * spf_table_device_buffers it needs no run. */
+int spf_table_levels_buffer(
+    spf_table* t, uint32_t local, void** levels, uint64_t* pitch, uint64_t* slot_bytes);
 /* spf_query_trace_paths over every local block of the table (each block on
  * its device, concurrently); dests and the counts are indexed by table
  * query.  Other ranks' blocks are not traced (their counts are 0).  Then
@@ -513,7 +603,9 @@ int spf_table_trace_expand(spf_table* t, const int32_t* node_labels);
 int spf_table_trace_expand_fetch(spf_table* t, uint64_t* cost, int32_t* labels);
 /* Gathered buffers on local device `local`: rows [world * cap][V] uint32
  * (cap = ceil(n / world)), masks [world * mask_cap] bytes in the layout of
- * spf_table_layout; NULL when that gather is off. */
+ * spf_table_layout; NULL when that gather is off (a SPF_T_GATHER_LEVELS
+ * table: rows is NULL until a run fell back to ROWS32 and the buffer exists;
+ * its content is current only while spf_table_row_form says ROWS32). */
 int spf_table_device_buffers(
     spf_table* t, uint32_t local, void** rows, void** masks, uint64_t* mask_cap_bytes);
 int spf_table_kernel_name(spf_table* t, uint32_t local, const char** name);

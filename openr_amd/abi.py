@@ -120,11 +120,18 @@ EXPORTED_SYMBOLS = (
     "spf_cgraph_patch_metrics",
     "spf_cgraph_device_graph",
     "spf_table_create_q",
+    "spf_query_pack_levels",
+    "spf_table_levels_layout",
+    "spf_table_expand_rows",
+    "spf_table_fetch_levels",
+    "spf_table_row_form",
+    "spf_table_levels_buffer",
 )
 
 SPF_CLUSTER_ID_BYTES = 128
 SPF_T_GATHER_ROWS = 0x100
 SPF_T_GATHER_NEXTHOPS = 0x200
+SPF_T_GATHER_LEVELS = 0x400
 
 SPF_DELTA_REMOVED = 1
 SPF_DELTA_ADDED = 2
@@ -333,9 +340,19 @@ def load():
         "spf_cgraph_patch_metrics": (C.c_int, [vp, u32, pu32, pu64]),
         "spf_cgraph_device_graph": (vp, [vp, u32]),
         "spf_table_create_q": (C.c_int, [vp, C.POINTER(_QueryDesc), u32, C.POINTER(vp)]),
+        "spf_query_pack_levels": (C.c_int, [vp, vp, C.c_size_t, vp]),
+        "spf_table_levels_layout": (C.c_int, [u32, u32, u32, pu64, pu64, pu64]),
+        "spf_table_expand_rows": (C.c_int, [vp, u32, u32, u32, vp, C.c_size_t]),
+        "spf_table_fetch_levels": (C.c_int, [vp, u32, u32, C.POINTER(C.c_uint8)]),
+        "spf_table_row_form": (C.c_int, [vp, pu32, pu32, pu64]),
+        "spf_table_levels_buffer": (C.c_int, [vp, u32, C.POINTER(vp), pu64, pu64]),
     }
     for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None and os.environ.get("OPENR_SPF_LIB"):
+            continue  # an older build loaded for an A/B: calling what it lacks still raises
+        if fn is None:
+            raise AttributeError(f"{LIB_PATH} lacks {name}: rebuild (python -m openr_amd.build)")
         fn.restype = res
         fn.argtypes = args
     _lib = lib
@@ -879,6 +896,15 @@ def table_layout(n: int, world: int, V: int, nh_bytes=None):
     return bf, mo[:n], int(cap.value)
 
 
+def table_levels_layout(n: int, world: int, V: int):
+    """spf_table_levels_layout (host only): (pitch, slot_bytes, trailer_off) of
+    the 8-bit level slots of a SPF_T_GATHER_LEVELS table."""
+    p, sb, to = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check_cl(load().spf_table_levels_layout(n, world, V, C.byref(p), C.byref(sb), C.byref(to)),
+              "spf_table_levels_layout")
+    return int(p.value), int(sb.value), int(to.value)
+
+
 def cluster_unique_id() -> bytes:
     buf = (C.c_uint8 * SPF_CLUSTER_ID_BYTES)()
     _check_cl(load().spf_cluster_unique_id(buf), "spf_cluster_unique_id")
@@ -895,10 +921,12 @@ class Cluster:
         h = C.c_void_p()
         if world is None:
             devs = (C.c_int * len(devices))(*devices)
+            self.devices = [int(d) for d in devices]
             _check_cl(lib.spf_cluster_create_local(len(devices), devs, C.byref(h)),
                       "spf_cluster_create_local")
         else:
             idb = (C.c_uint8 * SPF_CLUSTER_ID_BYTES)(*uid)
+            self.devices = [int(device)]
             _check_cl(lib.spf_cluster_create_rank(world, rank, idb, device, C.byref(h)),
                       "spf_cluster_create_rank")
         self.h = h
@@ -1071,3 +1099,53 @@ class Table:
         _check_cl(load().spf_table_device_buffers(self.h, local, C.byref(r), C.byref(m), C.byref(cap)),
                   "spf_table_device_buffers")
         return r.value, m.value, int(cap.value)
+
+    _FORMS = ("none", "rows32", "levels")
+
+    def row_form(self):
+        """spf_table_row_form: ("levels" | "rows32" | "none", scale, bytes each
+        rank received in the last run's row exchange).  Collective for a
+        SPF_T_GATHER_LEVELS table (it resolves the run's form)."""
+        f, s, b = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _check_cl(load().spf_table_row_form(self.h, C.byref(f), C.byref(s), C.byref(b)),
+                  "spf_table_row_form")
+        return self._FORMS[f.value], int(s.value), int(b.value)
+
+    def levels_layout(self):
+        """(pitch, slot_bytes, trailer_off) of this table's level slots."""
+        return table_levels_layout(self.n, self.cluster.world, self.V)
+
+    def levels_buffer(self, local: int = 0):
+        """(device pointer or None, pitch, slot_bytes) of the gathered level
+        rows on local device `local` (spf_table_levels_buffer)."""
+        p = C.c_void_p()
+        pitch, sb = C.c_uint64(), C.c_uint64()
+        _check_cl(load().spf_table_levels_buffer(self.h, local, C.byref(p), C.byref(pitch), C.byref(sb)),
+                  "spf_table_levels_buffer")
+        return p.value, int(pitch.value), int(sb.value)
+
+    def fetch_levels(self, first: int, count: int) -> np.ndarray:
+        """Raw 8-bit levels [count][V] of the gathered buffer (levels form
+        only): distance = level * scale, 255 = unreached."""
+        out = np.empty((count, self.V), dtype=np.uint8)
+        _check_cl(load().spf_table_fetch_levels(self.h, first, count, _p(out, C.c_uint8)),
+                  "spf_table_fetch_levels")
+        return out
+
+    def expand_rows(self, first: int, count: int, local: int = 0) -> np.ndarray:
+        """The uint32 rows of sources [first, first+count) expanded on the
+        device from the gathered buffer of local device `local`
+        (spf_table_expand_rows), whoever owns them; returned on the host."""
+        lib = load()
+        out = np.empty((count, self.V), dtype=np.uint32)
+        dev = self.cluster.devices[local]
+        buf = C.c_void_p()
+        _check(lib.spf_device_alloc(dev, max(out.nbytes, 4), C.byref(buf)), "spf_device_alloc")
+        try:
+            _check_cl(lib.spf_table_expand_rows(self.h, local, first, count, buf, self.V * 4),
+                      "spf_table_expand_rows")
+            self.sync()
+            _check(lib.spf_device_memcpy(dev, out.ctypes.data, buf, out.nbytes, 0), "spf_device_memcpy")
+        finally:
+            lib.spf_device_free(dev, buf)
+        return out

@@ -14,7 +14,12 @@
 // (SPF_T_GATHER_ROWS) and of the packed next-hop masks (SPF_T_GATHER_NEXTHOPS)
 // into equal-sized rank slots.  Without the gather flags the rows stay on
 // their owner device (a RouteDb needs only its own row; the host fetches
-// blocks directly).
+// blocks directly).  SPF_T_GATHER_LEVELS exchanges the rows as the MS-BFS
+// plan's 8-bit level rows instead (a quarter of the bytes, and no uint32 copy
+// into the slot); a run whose levels do not encode its distances -- a level
+// reached 255, or a block ran another plan -- is found from the slots'
+// trailers in spf_table_sync and exchanged as uint32 rows after all
+// (resolve_levels).
 //
 // This layer composes the single-device ABI (spf_graph_* / spf_query_*) with
 // RCCL; it launches no kernels of its own.
@@ -78,10 +83,17 @@ int cfail(int status, const std::string& what) {
 
 uint64_t roundup32(uint64_t x) { return (x + 31) & ~31ull; }
 
+// device scratch of spf_table_fetch_rows' expansions (SPF_T_GATHER_LEVELS)
+constexpr size_t kScratchBytes = 8u << 20;
+
 } // namespace
 
 // spf_device.hip (same library, not exported)
 extern "C" uint32_t spf_graph_live_queries_(const spf_graph* g);
+extern "C" int spf_graph_levels_capable_(const spf_graph* g, uint32_t unit);
+extern "C" int spf_levels_expand_(
+    void* stream, const uint8_t* lvl, size_t lvl_pitch, uint32_t rows, uint32_t V, uint32_t scale,
+    void* dst, size_t dst_pitch);
 
 struct spf_cluster {
   uint32_t world = 1;
@@ -118,12 +130,26 @@ struct spf_table {
     spf_graph* g = nullptr;
     spf_query* q = nullptr;
     std::vector<uint32_t> ign_off; // this block's ignore offsets, rebased to 0
-    uint32_t* rows = nullptr;  // gathered rows [world * cap][V] (GATHER_ROWS)
+    // gathered rows [world * cap][V] (GATHER_ROWS; GATHER_LEVELS: allocated by
+    // the first run that falls back to uint32 rows)
+    uint32_t* rows = nullptr;
+    uint8_t* lvls = nullptr;  // gathered level slots [world * lvl_slot bytes] (GATHER_LEVELS)
+    uint32_t* scratch = nullptr; // spf_table_fetch_rows: expanded rows of other ranks
+    // the fallback exchange of a GATHER_LEVELS run (e3 .. e4), and the last
+    // spf_table_expand_rows on this device (ex)
+    hipEvent_t e3 = nullptr, e4 = nullptr, ex = nullptr;
+    bool expanding = false;
     uint8_t* masks = nullptr; // gathered masks [world * mask_cap bytes] (GATHER_NEXTHOPS)
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   };
   std::vector<Local> local;
   bool ran = false;
+  // GATHER_LEVELS: slot geometry (spf_table_levels_layout) and the last run's
+  // form, decided by resolve_levels from the gathered trailers
+  uint64_t lvl_pitch = 0, lvl_slot = 0, lvl_trailer = 0;
+  bool resolved = false, fell_back = false;
+  uint32_t form = SPF_ROW_FORM_NONE;
+  std::vector<uint32_t> lvl_scale; // [world] scale of each rank's block (levels form)
   // spf_table_trace_paths: packed offsets of each local block's paths
   bool traced = false;
   std::vector<uint64_t> trace_link_base, trace_path_base;
@@ -164,6 +190,26 @@ int spf_table_layout(
   }
   if (mask_cap) {
     *mask_cap = cap;
+  }
+  return SPF_OK;
+}
+
+int spf_table_levels_layout(
+    uint32_t num_sources, uint32_t world, uint32_t num_nodes, uint64_t* pitch,
+    uint64_t* slot_bytes, uint64_t* trailer_off) {
+  if (world == 0 || (!pitch && !slot_bytes && !trailer_off)) {
+    return cfail(SPF_E_INVALID, "spf_table_levels_layout: world == 0 or no output");
+  }
+  const uint64_t p = ((uint64_t)num_nodes + 15) & ~15ull;
+  const uint64_t cap = ((uint64_t)num_sources + world - 1) / world;
+  if (pitch) {
+    *pitch = p;
+  }
+  if (trailer_off) {
+    *trailer_off = cap * p;
+  }
+  if (slot_bytes) {
+    *slot_bytes = cap * p + 16; // the four trailer words
   }
   return SPF_OK;
 }
@@ -275,7 +321,13 @@ static void free_table(spf_table* t) {
     if (L.masks) {
       (void)hipFree(L.masks);
     }
-    for (hipEvent_t e : {L.e0, L.e1, L.e2}) {
+    if (L.lvls) {
+      (void)hipFree(L.lvls);
+    }
+    if (L.scratch) {
+      (void)hipFree(L.scratch);
+    }
+    for (hipEvent_t e : {L.e0, L.e1, L.e2, L.e3, L.e4, L.ex}) {
       if (e) {
         (void)hipEventDestroy(e);
       }
@@ -378,8 +430,19 @@ static int table_init(
   if ((flags & SPF_T_GATHER_NEXTHOPS) && !(flags & SPF_F_NEXTHOPS)) {
     return cfail(SPF_E_INVALID, "spf_table_create: GATHER_NEXTHOPS needs SPF_F_NEXTHOPS");
   }
+  if ((flags & SPF_T_GATHER_LEVELS) && (flags & SPF_T_GATHER_ROWS)) {
+    return cfail(SPF_E_INVALID, "spf_table_create: GATHER_LEVELS with GATHER_ROWS (pick one)");
+  }
   if (num_sources && !sources) {
     return cfail(SPF_E_INVALID, "spf_table_create: null sources");
+  }
+  // level rows exist on the MS-BFS plan only: refuse what rules it out on
+  // every rank alike (the graph); a block's own plan is reported per run
+  if ((flags & SPF_T_GATHER_LEVELS) && !graphs.empty() &&
+      !spf_graph_levels_capable_(graphs[0], flags & SPF_F_UNIT_METRIC)) {
+    return cfail(SPF_E_UNSUPPORTED,
+                 "spf_table_create: GATHER_LEVELS needs a uniform metric (or SPF_F_UNIT_METRIC) on "
+                 "a graph the MS-BFS plan holds");
   }
   for (uint32_t i = 0; i < num_sources; ++i) {
     if (sources[i] >= V) {
@@ -398,6 +461,7 @@ static int table_init(
   t->V = V;
   t->n = num_sources;
   t->flags = flags;
+  t->form = (flags & SPF_T_GATHER_ROWS) ? SPF_ROW_FORM_ROWS32 : SPF_ROW_FORM_NONE;
   t->sources.assign(sources, sources + num_sources);
   t->cap = (num_sources + c->world - 1) / c->world;
   t->block_first.resize(c->world + 1);
@@ -459,6 +523,14 @@ static int table_init(
     if (flags & SPF_T_GATHER_NEXTHOPS) {
       CL_HIP(hipMalloc((void**)&L.masks, (size_t)c->world * t->mask_cap));
     }
+    if (flags & SPF_T_GATHER_LEVELS) {
+      CL_TRY(spf_table_levels_layout(num_sources, c->world, V, &t->lvl_pitch, &t->lvl_slot,
+                                     &t->lvl_trailer));
+      CL_HIP(hipMalloc((void**)&L.lvls, (size_t)c->world * t->lvl_slot));
+      CL_HIP(hipEventCreate(&L.e3));
+      CL_HIP(hipEventCreate(&L.e4));
+    }
+    CL_HIP(hipEventCreate(&L.ex));
     CL_HIP(hipEventCreate(&L.e0));
     CL_HIP(hipEventCreate(&L.e1));
     CL_HIP(hipEventCreate(&L.e2));
@@ -534,7 +606,11 @@ int spf_table_run(spf_table* t) {
     const uint64_t first = t->block_first[L.rank], count = t->block_first[L.rank + 1] - first;
     if (L.q) {
       CL_TRY(spf_query_run(L.q));
-      if (L.rows) {
+      if (L.lvls) {
+        // the level rows and this run's trailer instead of the uint32 rows
+        uint8_t* slot = L.lvls + (size_t)L.rank * t->lvl_slot;
+        CL_TRY(spf_query_pack_levels(L.q, slot, t->lvl_pitch, slot + t->lvl_trailer));
+      } else if (L.rows) {
         CL_TRY(spf_query_fetch_rows(L.q, 0, (uint32_t)count,
                                     L.rows + (size_t)L.rank * t->cap * t->V,
                                     (size_t)t->V * sizeof(uint32_t), 1));
@@ -549,17 +625,23 @@ int spf_table_run(spf_table* t) {
                               total * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
         // (total * 8 = the query's byte layout, <= mask_cap)
       }
+    } else if (L.lvls) {
+      // an empty block: a zero trailer
+      CL_HIP(hipMemsetAsync(L.lvls + (size_t)L.rank * t->lvl_slot + t->lvl_trailer, 0, 16, st));
     }
     CL_HIP(hipEventRecord(L.e1, st));
   }
   // 2. the exchange: in-place all-gathers into equal-sized rank slots
-  if (t->flags & (SPF_T_GATHER_ROWS | SPF_T_GATHER_NEXTHOPS)) {
+  if (t->flags & (SPF_T_GATHER_ROWS | SPF_T_GATHER_NEXTHOPS | SPF_T_GATHER_LEVELS)) {
     CL_NCCL(ncclGroupStart());
     for (size_t d = 0; d < t->local.size(); ++d) {
       auto& L = t->local[d];
       CL_HIP(hipSetDevice(L.device));
       hipStream_t st = (hipStream_t)spf_graph_get_stream(L.g);
-      if (L.rows) {
+      if (L.lvls) {
+        CL_NCCL(ncclAllGather(L.lvls + (size_t)L.rank * t->lvl_slot, L.lvls, t->lvl_slot,
+                              ncclUint8, c->comms[d], st));
+      } else if (L.rows) {
         const size_t cnt = (size_t)t->cap * t->V;
         CL_NCCL(ncclAllGather(L.rows + (size_t)L.rank * cnt, L.rows, cnt, ncclUint32,
                               c->comms[d], st));
@@ -576,8 +658,127 @@ int spf_table_run(spf_table* t) {
     CL_HIP(hipEventRecord(L.e2, (hipStream_t)spf_graph_get_stream(L.g)));
   }
   t->ran = true;
+  t->resolved = false;
+  t->fell_back = false;
+  for (auto& L : t->local) {
+    L.expanding = false; // (stream order: the run waited for it)
+  }
   return SPF_OK;
 }
+
+} // extern "C"
+
+// GATHER_LEVELS: decide the last run's form from the gathered trailers, and
+// exchange uint32 rows after all when the levels do not stand for them.
+// Every rank reads the same `world` trailers, so every rank takes the same
+// branch; the fallback's all-gather makes this a collective.
+static int resolve_levels(spf_table* t) {
+  if (!(t->flags & SPF_T_GATHER_LEVELS) || t->resolved || !t->ran) {
+    return SPF_OK;
+  }
+  spf_cluster* c = t->c;
+  for (auto& L : t->local) {
+    CL_HIP(hipSetDevice(L.device));
+    CL_HIP(hipEventSynchronize(L.e2));
+  }
+  // the trailers, from one local device: one strided copy of 16 * world bytes
+  std::vector<uint32_t> tr(4 * (size_t)c->world, 0);
+  {
+    auto& L = t->local[0];
+    CL_HIP(hipSetDevice(L.device));
+    if (c->world == 1) {
+      CL_HIP(hipMemcpy(tr.data(), L.lvls + t->lvl_trailer, 16, hipMemcpyDeviceToHost));
+    } else {
+      CL_HIP(hipMemcpy2D(tr.data(), 16, L.lvls + t->lvl_trailer, t->lvl_slot, 16, c->world,
+                         hipMemcpyDeviceToHost));
+    }
+  }
+  bool levels = true;
+  t->lvl_scale.assign(c->world, 0);
+  for (uint32_t r = 0; r < c->world; ++r) {
+    levels = levels && tr[4 * r] == 0;
+    t->lvl_scale[r] = tr[4 * r + 1];
+  }
+  if (levels) {
+    t->form = SPF_ROW_FORM_LEVELS;
+    t->resolved = true;
+    return SPF_OK;
+  }
+  // the fallback: exactly SPF_T_GATHER_ROWS' copy and exchange
+  for (auto& L : t->local) {
+    CL_HIP(hipSetDevice(L.device));
+    hipStream_t st = (hipStream_t)spf_graph_get_stream(L.g);
+    if (!L.rows) {
+      CL_HIP(hipMalloc((void**)&L.rows, (size_t)c->world * t->cap * t->V * sizeof(uint32_t)));
+    }
+    CL_HIP(hipEventRecord(L.e3, st));
+    if (L.q) {
+      const uint64_t count = t->block_first[L.rank + 1] - t->block_first[L.rank];
+      CL_TRY(spf_query_fetch_rows(L.q, 0, (uint32_t)count, L.rows + (size_t)L.rank * t->cap * t->V,
+                                  (size_t)t->V * sizeof(uint32_t), 1));
+    }
+  }
+  CL_NCCL(ncclGroupStart());
+  for (size_t d = 0; d < t->local.size(); ++d) {
+    auto& L = t->local[d];
+    CL_HIP(hipSetDevice(L.device));
+    const size_t cnt = (size_t)t->cap * t->V;
+    CL_NCCL(ncclAllGather(L.rows + (size_t)L.rank * cnt, L.rows, cnt, ncclUint32, c->comms[d],
+                          (hipStream_t)spf_graph_get_stream(L.g)));
+  }
+  CL_NCCL(ncclGroupEnd());
+  for (auto& L : t->local) {
+    CL_HIP(hipSetDevice(L.device));
+    CL_HIP(hipEventRecord(L.e4, (hipStream_t)spf_graph_get_stream(L.g)));
+  }
+  for (auto& L : t->local) {
+    CL_HIP(hipSetDevice(L.device));
+    CL_HIP(hipEventSynchronize(L.e4));
+  }
+  t->form = SPF_ROW_FORM_ROWS32;
+  t->fell_back = true;
+  t->resolved = true;
+  return SPF_OK;
+}
+
+// rank owning source index i
+static uint32_t owner_of(const spf_table* t, uint32_t i) {
+  const auto it = std::upper_bound(t->block_first.begin(), t->block_first.end(), (uint64_t)i);
+  return (uint32_t)(it - t->block_first.begin()) - 1;
+}
+
+// uint32 rows of sources [first, first + count) from the gathered buffer of
+// local device L into its device memory, on its graph stream (the run must
+// be resolved): the expand kernel per owner block in levels form, a strided
+// copy in rows32 form
+static int expand_gathered(
+    spf_table* t, spf_table::Local& L, uint32_t first, uint32_t count, void* dst,
+    size_t dst_pitch) {
+  CL_HIP(hipSetDevice(L.device));
+  hipStream_t st = (hipStream_t)spf_graph_get_stream(L.g);
+  uint32_t i = first;
+  while (i < first + count) {
+    const uint32_t r = owner_of(t, i);
+    const uint32_t bend = (uint32_t)std::min<uint64_t>(t->block_first[r + 1], first + count);
+    const uint64_t k = i - t->block_first[r]; // row within rank r's slot
+    uint8_t* out = (uint8_t*)dst + (size_t)(i - first) * dst_pitch;
+    if (t->form == SPF_ROW_FORM_LEVELS) {
+      const int s = spf_levels_expand_(st, L.lvls + (size_t)r * t->lvl_slot + k * t->lvl_pitch,
+                                       t->lvl_pitch, bend - i, t->V, t->lvl_scale[r], out, dst_pitch);
+      if (s != SPF_OK) {
+        return cfail(s, std::string("spf_levels_expand: ") + spf_last_error_detail());
+      }
+    } else if (t->V) {
+      CL_HIP(hipMemcpy2DAsync(out, dst_pitch, L.rows + ((size_t)r * t->cap + k) * t->V,
+                              (size_t)t->V * 4, (size_t)t->V * 4, bend - i,
+                              hipMemcpyDeviceToDevice, st));
+    }
+    i = bend;
+  }
+  return SPF_OK;
+}
+
+extern "C" {
 
 int spf_table_sync(spf_table* t) {
   if (!t) {
@@ -587,6 +788,14 @@ int spf_table_sync(spf_table* t) {
     CL_HIP(hipSetDevice(L.device));
     CL_HIP(hipEventSynchronize(L.e2));
   }
+  CL_TRY(resolve_levels(t));
+  for (auto& L : t->local) {
+    if (L.expanding) {
+      CL_HIP(hipSetDevice(L.device));
+      CL_HIP(hipEventSynchronize(L.ex));
+      L.expanding = false;
+    }
+  }
   return SPF_OK;
 }
 
@@ -594,12 +803,18 @@ int spf_table_elapsed_ms(spf_table* t, float* compute_ms, float* gather_ms) {
   if (!t || !t->ran) {
     return cfail(SPF_E_INVALID, "spf_table_elapsed_ms: table has not run");
   }
+  CL_TRY(resolve_levels(t)); // the fallback exchange counts as gather time
   float cm = 0, gm = 0;
   for (auto& L : t->local) {
     CL_HIP(hipSetDevice(L.device));
     float a = 0, b = 0;
     CL_HIP(hipEventElapsedTime(&a, L.e0, L.e1));
     CL_HIP(hipEventElapsedTime(&b, L.e1, L.e2));
+    if (t->fell_back) {
+      float f = 0;
+      CL_HIP(hipEventElapsedTime(&f, L.e3, L.e4));
+      b += f;
+    }
     cm = std::max(cm, a);
     gm = std::max(gm, b);
   }
@@ -639,12 +854,6 @@ int spf_table_nh_bytes(const spf_table* t, uint32_t i) {
   return (int)t->nbytes[i];
 }
 
-// rank owning source index i
-static uint32_t owner_of(const spf_table* t, uint32_t i) {
-  const auto it = std::upper_bound(t->block_first.begin(), t->block_first.end(), (uint64_t)i);
-  return (uint32_t)(it - t->block_first.begin()) - 1;
-}
-
 int spf_table_fetch_rows(spf_table* t, uint32_t first, uint32_t count, uint32_t* dst) {
   SPF_ABI_RANGE_CLUSTER("spf_table_fetch_rows");
   if (!t || !dst || first + (uint64_t)count > t->n) {
@@ -661,7 +870,29 @@ int spf_table_fetch_rows(spf_table* t, uint32_t first, uint32_t count, uint32_t*
         src = &L;
       }
     }
-    if (!src || !src->q) {
+    if ((!src || !src->q) && (t->flags & SPF_T_GATHER_LEVELS)) {
+      // another rank's rows: expanded from the gathered copy into a bounded
+      // device scratch, a batch of rows at a time
+      if (!t->ran) {
+        return cfail(SPF_E_INVALID, "spf_table_fetch_rows: table has not run");
+      }
+      CL_TRY(resolve_levels(t));
+      auto& L = t->local[0];
+      CL_HIP(hipSetDevice(L.device));
+      const size_t rowb = (size_t)t->V * sizeof(uint32_t);
+      const uint32_t batch = (uint32_t)std::max<size_t>(1, kScratchBytes / std::max<size_t>(rowb, 1));
+      if (!L.scratch) {
+        CL_HIP(hipMalloc((void**)&L.scratch, std::max<size_t>(rowb, 4) * std::min(batch, t->cap)));
+      }
+      hipStream_t st = (hipStream_t)spf_graph_get_stream(L.g);
+      for (uint32_t k = i; k < bend; k += batch) {
+        const uint32_t m = std::min(batch, bend - k);
+        CL_TRY(expand_gathered(t, L, k, m, L.scratch, rowb));
+        CL_HIP(hipMemcpyAsync(dst + (size_t)(k - first) * t->V, L.scratch, (size_t)m * rowb,
+                              hipMemcpyDeviceToHost, st));
+        CL_HIP(hipStreamSynchronize(st));
+      }
+    } else if (!src || !src->q) {
       if (!(t->flags & SPF_T_GATHER_ROWS)) {
         return cfail(SPF_E_UNSUPPORTED, "spf_table_fetch_rows: rows of another rank (no gather)");
       }
@@ -918,6 +1149,109 @@ int spf_table_device_buffers(
   }
   if (mask_cap_bytes) {
     *mask_cap_bytes = t->mask_cap;
+  }
+  return SPF_OK;
+}
+
+int spf_table_row_form(spf_table* t, uint32_t* form, uint32_t* scale, uint64_t* gathered_bytes) {
+  if (!t) {
+    return cfail(SPF_E_INVALID, "spf_table_row_form: null table");
+  }
+  if (!t->ran) {
+    return cfail(SPF_E_INVALID, "spf_table_row_form: table has not run");
+  }
+  CL_TRY(resolve_levels(t));
+  const uint64_t rows32 = (uint64_t)t->c->world * t->cap * t->V * sizeof(uint32_t);
+  uint32_t f = SPF_ROW_FORM_NONE, sc = 0;
+  uint64_t bytes = 0;
+  if (t->flags & SPF_T_GATHER_LEVELS) {
+    f = t->form;
+    bytes = (uint64_t)t->c->world * t->lvl_slot + (t->fell_back ? rows32 : 0);
+    if (f == SPF_ROW_FORM_LEVELS) {
+      for (uint32_t s : t->lvl_scale) {
+        sc = sc ? sc : s; // (an empty block's trailer holds 0)
+      }
+    }
+  } else if (t->flags & SPF_T_GATHER_ROWS) {
+    f = SPF_ROW_FORM_ROWS32;
+    bytes = rows32;
+  }
+  if (form) {
+    *form = f;
+  }
+  if (scale) {
+    *scale = sc;
+  }
+  if (gathered_bytes) {
+    *gathered_bytes = bytes;
+  }
+  return SPF_OK;
+}
+
+int spf_table_expand_rows(
+    spf_table* t, uint32_t local, uint32_t first, uint32_t count, void* dst_dev,
+    size_t dst_pitch) {
+  SPF_ABI_RANGE_CLUSTER("spf_table_expand_rows");
+  if (!t || local >= t->local.size() || first + (uint64_t)count > t->n || (count && !dst_dev) ||
+      dst_pitch < (size_t)t->V * 4 || (dst_pitch & 3) || ((uintptr_t)dst_dev & 3)) {
+    return cfail(SPF_E_INVALID, "spf_table_expand_rows: bad device index, range, pointer or pitch");
+  }
+  if (!t->ran) {
+    return cfail(SPF_E_INVALID, "spf_table_expand_rows: table has not run");
+  }
+  if (!(t->flags & (SPF_T_GATHER_LEVELS | SPF_T_GATHER_ROWS))) {
+    return cfail(SPF_E_UNSUPPORTED, "spf_table_expand_rows: the table gathers no rows");
+  }
+  CL_TRY(resolve_levels(t));
+  auto& L = t->local[local];
+  if (count) {
+    CL_TRY(expand_gathered(t, L, first, count, dst_dev, dst_pitch));
+  }
+  CL_HIP(hipSetDevice(L.device));
+  CL_HIP(hipEventRecord(L.ex, (hipStream_t)spf_graph_get_stream(L.g)));
+  L.expanding = true;
+  return SPF_OK;
+}
+
+int spf_table_fetch_levels(spf_table* t, uint32_t first, uint32_t count, uint8_t* dst) {
+  SPF_ABI_RANGE_CLUSTER("spf_table_fetch_levels");
+  if (!t || !dst || first + (uint64_t)count > t->n) {
+    return cfail(SPF_E_INVALID, "spf_table_fetch_levels: bad range");
+  }
+  if (!t->ran) {
+    return cfail(SPF_E_INVALID, "spf_table_fetch_levels: table has not run");
+  }
+  CL_TRY(resolve_levels(t));
+  if (!(t->flags & SPF_T_GATHER_LEVELS) || t->form != SPF_ROW_FORM_LEVELS) {
+    return cfail(SPF_E_UNSUPPORTED, "spf_table_fetch_levels: the last run's rows are not in levels form");
+  }
+  const auto& L = t->local[0];
+  CL_HIP(hipSetDevice(L.device));
+  uint32_t i = first;
+  while (i < first + count && t->V) {
+    const uint32_t r = owner_of(t, i);
+    const uint32_t bend = (uint32_t)std::min<uint64_t>(t->block_first[r + 1], first + count);
+    CL_HIP(hipMemcpy2D(dst + (size_t)(i - first) * t->V, t->V,
+                       L.lvls + (size_t)r * t->lvl_slot + (i - t->block_first[r]) * t->lvl_pitch,
+                       t->lvl_pitch, t->V, bend - i, hipMemcpyDeviceToHost));
+    i = bend;
+  }
+  return SPF_OK;
+}
+
+int spf_table_levels_buffer(
+    spf_table* t, uint32_t local, void** levels, uint64_t* pitch, uint64_t* slot_bytes) {
+  if (!t || local >= t->local.size()) {
+    return cfail(SPF_E_INVALID, "spf_table_levels_buffer: bad local index");
+  }
+  if (levels) {
+    *levels = t->local[local].lvls;
+  }
+  if (pitch) {
+    *pitch = t->lvl_pitch;
+  }
+  if (slot_bytes) {
+    *slot_bytes = t->lvl_slot;
   }
   return SPF_OK;
 }

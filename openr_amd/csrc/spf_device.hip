@@ -12594,9 +12594,168 @@ int run_plan_kernels(spf_query* q) {
   }
 }
 
+// ---- 8-bit level rows as the exchange form of an all-sources table
+// (SPF_T_GATHER_LEVELS, spf_cluster.hip) ----
+
+// u8 level rows -> u32 distance rows: lvl * scale, 255 -> unreached.  One
+// block per (row, 1,024-node chunk); each lane loads 4 level bytes (one u32)
+// and stores one uint4, so a wave reads 256 and writes 1,024 contiguous bytes
+// of one row (the shape profiles/calib measured fastest; 16 levels per lane
+// would store four 16-byte pieces 64 bytes apart).  The last group of a row
+// whose V is no multiple of 4 reads and writes its 1..3 entries one by one:
+// the pad bytes [V, lvl_pitch) are never read and nothing past byte 4V of a
+// destination row is written (the next row may start right there).
+constexpr uint32_t kLxThreads = 256, kLxChunk = 4 * kLxThreads;
+
+struct LvlExpandArgs {
+  const uint8_t* lvl; // [rows][lvl_pitch]
+  uint8_t* dst;       // [rows][dst_pitch] bytes, 4V used per row
+  uint64_t lvl_pitch, dst_pitch;
+  uint32_t V, nchunks, scale;
+  uint32_t ld4; // level base and pitch 4-byte aligned: one u32 load per lane
+  uint32_t st16; // destination base and pitch 16-byte aligned: uint4 stores
+};
+
+__global__ __launch_bounds__(kLxThreads) void spf_levels_expand_kernel(LvlExpandArgs a) {
+  const uint32_t row = blockIdx.x / a.nchunks, ch = blockIdx.x - row * a.nchunks;
+  const uint32_t v0 = ch * kLxChunk + 4u * threadIdx.x;
+  if (v0 >= a.V) {
+    return;
+  }
+  const uint8_t* src = a.lvl + (size_t)row * a.lvl_pitch + v0;
+  uint32_t* out = reinterpret_cast<uint32_t*>(a.dst + (size_t)row * a.dst_pitch) + v0;
+  const uint32_t n = a.V - v0 < 4u ? a.V - v0 : 4u;
+  uint32_t x = 0;
+  if (n == 4 && a.ld4) {
+    x = *reinterpret_cast<const uint32_t*>(src);
+  } else {
+    for (uint32_t k = 0; k < n; ++k) {
+      x |= (uint32_t)src[k] << (8 * k);
+    }
+  }
+  uint32_t d[4];
+#pragma unroll
+  for (uint32_t k = 0; k < 4; ++k) {
+    const uint32_t l = (x >> (8 * k)) & 0xFFu;
+    d[k] = l == 255u ? kInf32 : l * a.scale;
+  }
+  if (n == 4 && a.st16) {
+    *reinterpret_cast<uint4*>(out) = make_uint4(d[0], d[1], d[2], d[3]);
+  } else {
+    for (uint32_t k = 0; k < n; ++k) {
+      out[k] = d[k];
+    }
+  }
+}
+
+// The 16-byte trailer of a level slot: flags | the run's "deep" bit, scale,
+// row count, 0.  ms_flag: the flag word the run's MS-BFS used (nullptr: none).
+__global__ void spf_levels_trailer_kernel(
+    const uint32_t* ms_flag, uint32_t flags, uint32_t scale, uint32_t rows, uint32_t* trailer) {
+  if (threadIdx.x < 4) {
+    const uint32_t deep = ms_flag ? (ms_flag[0] & 1u) : 0u;
+    const uint32_t w[4] = {flags | deep, scale, rows, 0u};
+    trailer[threadIdx.x] = w[threadIdx.x];
+  }
+}
+
+// a query whose level rows [0, nq) encode its distances exactly (while no
+// level reaches 255): the plain MS-BFS plan.  Not the zero-metric variant
+// tables (a source's row lives in its variant's table), not a what-if batch
+// behind a screen (screened rows are copied from the baseline's distances).
+inline bool has_level_rows(const spf_query* q) {
+  return q->dist == DistPlan::MsBfs && !q->zvars && !q->base && q->d_lvl && q->d_flags;
+}
+
 } // namespace
 
 extern "C" {
+
+// SPF_T_GATHER_LEVELS at table creation (spf_cluster.hip; not exported): can
+// a batch on this graph ever run the MS-BFS plan?  Only facts of the graph,
+// equal on every rank.
+__attribute__((visibility("hidden"))) int spf_graph_levels_capable_(
+    const spf_graph* g, uint32_t unit) {
+  if (!g || g->V > kMsThreads * kMsMaxK || 2 * (size_t)g->V * 4 > kLdsLimit) {
+    return 0;
+  }
+  if (unit || g->uniform != 0) {
+    return 1;
+  }
+  std::vector<ZeroLink> zl;
+  uint32_t zc = 0;
+  return zero_plan_links(g, zl, zc) ? 1 : 0; // (its blocks report "no level rows" per run)
+}
+
+// u8 level rows to u32 rows on `stream` of the current device (the expand
+// step of SPF_T_GATHER_LEVELS readers, spf_cluster.hip; not exported).
+__attribute__((visibility("hidden"))) int spf_levels_expand_(
+    void* stream, const uint8_t* lvl, size_t lvl_pitch, uint32_t rows, uint32_t V, uint32_t scale,
+    void* dst, size_t dst_pitch) {
+  if (!lvl || !dst || lvl_pitch < V || dst_pitch < (size_t)V * 4 || (dst_pitch & 3) ||
+      ((uintptr_t)dst & 3)) {
+    return fail(SPF_E_INVALID, "level expansion: bad pitch or alignment");
+  }
+  if (!rows || !V) {
+    return SPF_OK;
+  }
+  LvlExpandArgs a;
+  a.lvl_pitch = lvl_pitch;
+  a.dst_pitch = dst_pitch;
+  a.V = V;
+  a.nchunks = (V + kLxChunk - 1) / kLxChunk;
+  a.scale = scale;
+  a.ld4 = (((uintptr_t)lvl | lvl_pitch) & 3) == 0;
+  a.st16 = (((uintptr_t)dst | dst_pitch) & 15) == 0;
+  // one block per (row, chunk), at most 2^31 - 1 blocks per launch
+  const uint32_t step = std::max<uint32_t>(1, 0x7FFFFFFFu / a.nchunks);
+  for (uint32_t r = 0; r < rows; r += step) {
+    const uint32_t m = std::min(step, rows - r);
+    a.lvl = lvl + (size_t)r * lvl_pitch;
+    a.dst = (uint8_t*)dst + (size_t)r * dst_pitch;
+    SPF_LAUNCH(spf_levels_expand_kernel, dim3(m * a.nchunks), dim3(kLxThreads), 0,
+               (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  return SPF_OK;
+}
+
+int spf_query_pack_levels(spf_query* q, void* dst_dev, size_t dst_pitch, void* trailer_dev) {
+  SPF_ABI_RANGE("spf_query_pack_levels");
+  if (!q || !trailer_dev || ((uintptr_t)trailer_dev & 3)) {
+    return fail(SPF_E_INVALID, "null query or trailer");
+  }
+  if (!q->ran) {
+    return fail(SPF_E_INVALID, "query has not run");
+  }
+  spf_graph* g = q->g;
+  const bool have = has_level_rows(q) && q->nq && g->V;
+  const uint32_t scale = (q->flags & SPF_F_UNIT_METRIC) ? 1u : g->uniform;
+  if (have && (!dst_dev || dst_pitch < g->V)) {
+    return fail(SPF_E_INVALID, "level rows: no destination or pitch < V");
+  }
+  HIP_TRY(hipSetDevice(g->device));
+  if (have && scale) {
+    // rows [0, nq) of the level table (the helper rows behind them stay)
+    if (dst_pitch == q->Vp8) {
+      HIP_TRY(hipMemcpyAsync(dst_dev, q->d_lvl, (size_t)q->nq * q->Vp8, hipMemcpyDeviceToDevice,
+                             g->stream));
+    } else {
+      HIP_TRY(hipMemcpy2DAsync(dst_dev, dst_pitch, q->d_lvl, q->Vp8, g->V, q->nq,
+                               hipMemcpyDeviceToDevice, g->stream));
+    }
+    SPF_LAUNCH(spf_levels_trailer_kernel, dim3(1), dim3(64), 0, g->stream,
+               (const uint32_t*)(q->d_flags + q->ms_par), 0u, scale, q->nq, (uint32_t*)trailer_dev);
+  } else {
+    // another plan, variant tables, 64-bit rows: bit 1, no level rows (an
+    // empty batch has nothing to report: a zero trailer)
+    SPF_LAUNCH(spf_levels_trailer_kernel, dim3(1), dim3(64), 0, g->stream,
+               (const uint32_t*)nullptr, q->nq && g->V ? 2u : 0u, 0u, q->nq,
+               (uint32_t*)trailer_dev);
+  }
+  HIP_TRY(hipGetLastError());
+  return SPF_OK;
+}
 
 int spf_query_run(spf_query* q) {
   SPF_ABI_RANGE("spf_query_run");
