@@ -93,6 +93,7 @@ namespace {
 
 constexpr uint32_t kBlock = 512;           // threads per workgroup (8 waves)
 constexpr uint32_t kWaves = kBlock / 64;
+constexpr uint32_t kDstepThreads = 1024;   // delta-stepping workgroup (spf_dstep_kernel)
 constexpr uint32_t kInf32 = 0xFFFFFFFFu;
 // host passes over the CSR go parallel from this many edges per thread
 constexpr size_t kHostMinEdges = 1u << 14;
@@ -152,6 +153,38 @@ uint32_t env_flag(const char* name, uint32_t dflt) {
 uint32_t env_u32(const char* name, uint32_t dflt) {
   const char* v = getenv(name);
   return v ? (uint32_t)strtoul(v, nullptr, 10) : dflt;
+}
+
+// signed value from the environment
+int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+
+// override from the environment clamped to [0, hi]; -1 = unset
+int env_clamped(const char* name, int hi) {
+  const char* v = getenv(name);
+  return v ? std::min(hi, std::max(0, atoi(v))) : -1;
+}
+
+// OPENR_SPF_MSBFS: the multi-source BFS plan's batch width (32 / 64), 0 = off
+int env_msbfs_width() {
+  return env_int("OPENR_SPF_MSBFS", 64);
+}
+
+// OPENR_SPF_DSTEP, set to anything: no delta-stepping plan
+bool env_dstep_off() {
+  return getenv("OPENR_SPF_DSTEP") != nullptr;
+}
+
+// OPENR_SPF_DSTEP_SHIFT: the delta-stepping bucket width (2^shift), -1 = unset
+int env_dstep_shift() {
+  return env_clamped("OPENR_SPF_DSTEP_SHIFT", 24);
+}
+
+// OPENR_SPF_DSTEP_STATS=1: event counts of the delta-stepping kernels on stderr
+bool env_dstep_stats() {
+  return env_int("OPENR_SPF_DSTEP_STATS", 0) == 1;
 }
 
 int fail(int code, const std::string& what) {
@@ -296,44 +329,30 @@ __device__ __forceinline__ void nh_store(uint8_t* row, uint32_t B, uint32_t W, u
   }
 }
 
-typedef uint32_t nt_u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t nt_u32x4 __attribute__((ext_vector_type(4)));
-
-// a streaming (write-once, never re-read by this pass) store: NT = true marks
-// it non-temporal so the output rows do not evict the level rows the other
-// blocks of the pass re-read from L2
-template <typename T>
-__device__ __forceinline__ void st_stream(T* p, T v, bool nt) {
-  if (nt) {
-    __builtin_nontemporal_store(v, p);
-  } else {
-    *p = v;
-  }
-}
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // single-word masks of nodes v0..v0+3 (v0 % 4 == 0) of a narrow row (B < 8):
 // one 4 / 8 / 16-byte store when all four nodes exist
 __device__ __forceinline__ void nh_store4_narrow(uint8_t* row, uint32_t B, uint32_t v0,
-                                                 uint32_t V, const uint64_t (&x)[4],
-                                                 bool nt = false) {
+                                                 uint32_t V, const uint64_t (&x)[4]) {
   if (v0 + 4 <= V) {
     if (B == 1) {
-      st_stream(reinterpret_cast<uint32_t*>(row + v0),
-                (uint32_t)(x[0] & 0xFFu) | (uint32_t)(x[1] & 0xFFu) << 8 |
-                    (uint32_t)(x[2] & 0xFFu) << 16 | (uint32_t)(x[3] & 0xFFu) << 24,
-                nt);
+      *reinterpret_cast<uint32_t*>(row + v0) =
+          (uint32_t)(x[0] & 0xFFu) | (uint32_t)(x[1] & 0xFFu) << 8 |
+          (uint32_t)(x[2] & 0xFFu) << 16 | (uint32_t)(x[3] & 0xFFu) << 24;
     } else if (B == 2) {
-      nt_u32x2 w;
+      u32x2 w;
       w.x = (uint32_t)(x[0] & 0xFFFFu) | (uint32_t)(x[1] & 0xFFFFu) << 16;
       w.y = (uint32_t)(x[2] & 0xFFFFu) | (uint32_t)(x[3] & 0xFFFFu) << 16;
-      st_stream(reinterpret_cast<nt_u32x2*>(row + 2 * (size_t)v0), w, nt);
+      *reinterpret_cast<u32x2*>(row + 2 * (size_t)v0) = w;
     } else {
-      nt_u32x4 w;
+      u32x4 w;
       w.x = (uint32_t)x[0];
       w.y = (uint32_t)x[1];
       w.z = (uint32_t)x[2];
       w.w = (uint32_t)x[3];
-      st_stream(reinterpret_cast<nt_u32x4*>(row + 4 * (size_t)v0), w, nt);
+      *reinterpret_cast<u32x4*>(row + 4 * (size_t)v0) = w;
     }
     return;
   }
@@ -1810,8 +1829,10 @@ __device__ __forceinline__ uint32_t dl_field(uint64_t x, uint32_t k) {
   return (uint32_t)(x >> (12 * k)) & 0xFFFu;
 }
 
-template <uint32_t BS, uint32_t G, bool PF>
+template <uint32_t BS>
 __global__ __launch_bounds__(BS) void spf_dlds_kernel(DldsArgs a) {
+  // lanes per expanded node (100k WAN: 4 measured fastest of 1 / 2 / 4 / 8)
+  constexpr uint32_t G = 4;
   extern __shared__ __align__(16) uint64_t fld[];
   const uint32_t V = a.V, nw = (V + 4) / 5;
   uint32_t* ctl = reinterpret_cast<uint32_t*>(fld + nw);
@@ -1903,11 +1924,11 @@ __global__ __launch_bounds__(BS) void spf_dlds_kernel(DldsArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
       }
-      // EXPAND qc[0, len).  PF: a group keeps two nodes ahead in flight —
-      // the next node's edge chunks and the one after's row range are loaded
+      // EXPAND qc[0, len).  A group keeps two nodes ahead in flight — the
+      // next node's edge chunks and the one after's row range are loaded
       // before the current node's relaxations (LDS work) run, so a group
       // waits for at most one HBM round trip per node instead of two
-      // (header, then chunks); without PF only the next header is early.
+      // (header, then chunks).
       uint32_t* cnt = ctl + ph;
       {
         // relax the (up to) 8 edges of a lane's two chunks of node u
@@ -1996,33 +2017,25 @@ __global__ __launch_bounds__(BS) void spf_dlds_kernel(DldsArgs a) {
         }
         uint4 xc[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
         uint32_t nbeg = 0, nend = 0, ntrb = 0;
-        if constexpr (PF) {
-          if (u != kInf32 && expands(u, trb)) {
-            load_chunks((beg >> 2) + lg, end, xc);
-          }
-          if (nu != kInf32) {
-            nbeg = a.row[nu];
-            nend = a.row[nu + 1];
-            ntrb = a.trbits[nu >> 5];
-          }
+        if (u != kInf32 && expands(u, trb)) {
+          load_chunks((beg >> 2) + lg, end, xc);
+        }
+        if (nu != kInf32) {
+          nbeg = a.row[nu];
+          nend = a.row[nu + 1];
+          ntrb = a.trbits[nu >> 5];
         }
         while (u != kInf32) {
           const uint32_t nnu = i + 2 * ngrp < len ? qc[i + 2 * ngrp] : kInf32;
           uint4 xn[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-          uint32_t bb = 0, ee = 0, tt = 0; // the node after next (PF), else the next
-          if constexpr (PF) {
-            if (nu != kInf32 && expands(nu, ntrb)) {
-              load_chunks((nbeg >> 2) + lg, nend, xn);
-            }
-            if (nnu != kInf32) {
-              bb = a.row[nnu];
-              ee = a.row[nnu + 1];
-              tt = a.trbits[nnu >> 5];
-            }
-          } else if (nu != kInf32) {
-            bb = a.row[nu];
-            ee = a.row[nu + 1];
-            tt = a.trbits[nu >> 5];
+          uint32_t bb = 0, ee = 0, tt = 0; // the node after next
+          if (nu != kInf32 && expands(nu, ntrb)) {
+            load_chunks((nbeg >> 2) + lg, nend, xn);
+          }
+          if (nnu != kInf32) {
+            bb = a.row[nnu];
+            ee = a.row[nnu + 1];
+            tt = a.trbits[nnu >> 5];
           }
           if (expands(u, trb)) {
             const uint32_t du = dl_field(ld(u / 5), u % 5);
@@ -2031,11 +2044,8 @@ __global__ __launch_bounds__(BS) void spf_dlds_kernel(DldsArgs a) {
               st[1] += end - beg;
             }
             uint32_t kc = (beg >> 2) + lg;
-            if constexpr (PF) {
-              relax_chunks(xc, kc, beg, end, du);
-              kc += 2 * G;
-            }
-            for (; 4 * kc < end; kc += 2 * G) {
+            relax_chunks(xc, kc, beg, end, du);
+            for (kc += 2 * G; 4 * kc < end; kc += 2 * G) {
               uint4 x[2];
               load_chunks(kc, end, x);
               relax_chunks(x, kc, beg, end, du);
@@ -2044,20 +2054,14 @@ __global__ __launch_bounds__(BS) void spf_dlds_kernel(DldsArgs a) {
           i += ngrp;
           u = nu;
           nu = nnu;
-          if constexpr (PF) {
-            beg = nbeg;
-            end = nend;
-            trb = ntrb;
-            nbeg = bb;
-            nend = ee;
-            ntrb = tt;
-            xc[0] = xn[0];
-            xc[1] = xn[1];
-          } else {
-            beg = bb;
-            end = ee;
-            trb = tt;
-          }
+          beg = nbeg;
+          end = nend;
+          trb = ntrb;
+          nbeg = bb;
+          nend = ee;
+          ntrb = tt;
+          xc[0] = xn[0];
+          xc[1] = xn[1];
         }
       }
       // the next phase's counter was last read two phases ago (before the
@@ -2690,9 +2694,6 @@ __global__ __launch_bounds__(kNhThreads) void spf_nh_rows_kernel(NhRowsArgs a) {
 // as 32-bit rows plus an 8-bit level row that the next-hop pass streams
 // instead of the 32-bit distances.
 
-#ifndef OPENR_MS_UNROLL8
-#define OPENR_MS_UNROLL8 1
-#endif
 constexpr uint32_t kMsThreads = 1024;
 constexpr uint32_t kMsShallowLevel = 127;
 constexpr uint32_t kMsMaxK = 20; // nodes per thread -> V <= 20480 (32-bit batches above 10,240 nodes: the
@@ -2743,8 +2744,6 @@ struct MsBfsArgs {
   const uint32_t* ign_flag = nullptr;
   uint32_t E = 0;
   uint32_t nfw = 0;
-  // measurement only (OPENR_MS_NOREC=1): the BFS without its row stores
-  uint32_t norec = 0;
   // per batch: one node that stays non-transit in this batch (kInf32 none;
   // nullptr: no such node) -- the what-if first-hop rows, BFS levels from a
   // source's neighbours through every node but that source
@@ -2785,9 +2784,6 @@ __global__ __launch_bounds__(256) void spf_ms_ign_kernel(
 template <typename MT>
 __device__ __forceinline__ void ms_record(
     const MsBfsArgs& a, uint32_t q0, uint32_t v, MT bits, uint32_t level) {
-  if (a.norec) {
-    return;
-  }
   const uint32_t d = level * a.scale;
   const uint8_t l8 = level < 255 ? (uint8_t)level : (uint8_t)255;
   if (level >= kMsShallowLevel && bits) {
@@ -2978,14 +2974,12 @@ __global__ __launch_bounds__(kMsThreads) void spf_msbfs_kernel(MsBfsArgs a) {
           const uint32_t beg = a.row[v], end = a.row[v + 1];
           MT acc = 0;
           uint32_t e = beg;
-#if OPENR_MS_UNROLL8
           for (; e + 8 <= end; e += 8) {
             const uint4 c0 = {a.col[e], a.col[e + 1], a.col[e + 2], a.col[e + 3]};
             const uint4 c1 = {a.col[e + 4], a.col[e + 5], a.col[e + 6], a.col[e + 7]};
             acc |= cur[c0.x] | cur[c0.y] | cur[c0.z] | cur[c0.w] | cur[c1.x] | cur[c1.y] |
                    cur[c1.z] | cur[c1.w];
           }
-#endif
           for (; e + 4 <= end; e += 4) {
             const uint32_t u0 = a.col[e], u1 = a.col[e + 1], u2 = a.col[e + 2],
                            u3 = a.col[e + 3];
@@ -3248,8 +3242,6 @@ struct NhLevelsArgs {
   uint32_t Vp8;
   uint32_t nq;
   uint32_t scale;
-  uint32_t xcd_swizzle; // 1: XCD-aware block order (OPENR_NL_XCD; default off: 0.69 -> 0.92 ms on the fabric, profiles/r03b)
-  uint32_t held_words;  // 1: 2/3-word masks stored node-major from registers (OPENR_NL_HELD)
   // zero-metric plan: source q reads its own and its neighbours' rows from
   // variant table zvar[q] (lvl + zvar[q] * lvl_vstride, dist + zvar[q] *
   // dist_vstride); nullptr: one table
@@ -3260,14 +3252,6 @@ struct NhLevelsArgs {
   // level 255 (lvl * scale) into dist_w and reads neighbour distances from
   // the level byte when it is below 255
   uint32_t* dist_w;
-  // held kernel work order (OPENR_NL_ORDER=1): hardware block b runs item
-  // held_order[b] = q * held_nch + chunk (kInf32: none); nullptr = the
-  // chunk-major default
-  const uint32_t* held_order = nullptr;
-  uint32_t held_nch = 0;
-  // OPENR_NL_NT=1: the byte-SIMD pass's mask and distance rows as
-  // non-temporal stores
-  uint32_t nt_store = 0;
 };
 
 constexpr uint32_t kNlThreads = 256;
@@ -3281,10 +3265,7 @@ constexpr uint32_t kNlChunk = kNlThreads * kNlPer;
 // and the neighbour rows are loaded kNlUnroll at a time, so a block keeps
 // several independent row loads in flight instead of one dependent chain
 // (nbrs -> row_of -> trbits -> row) per neighbour.
-#ifndef OPENR_NL_UNROLL
-#define OPENR_NL_UNROLL 8
-#endif
-constexpr uint32_t kNlUnroll = OPENR_NL_UNROLL;
+constexpr uint32_t kNlUnroll = 8;
 constexpr uint32_t kNlStage = 1024; // neighbours staged per pass
 
 template <bool WIDE>
@@ -3650,20 +3631,7 @@ __device__ __forceinline__ void nl_body_multi(
 // merge the pieces of a line.
 // chunks of 1024 nodes swept by one block (measured on the fabric: 2 ->
 // 0.676 ms, 4 -> 0.682, 16 = whole rows -> 0.710; kNlUnroll 4 / 16 slower)
-#ifndef OPENR_NL_CPB
-#define OPENR_NL_CPB 2
-#endif
-constexpr uint32_t kNlChunksPerBlock = OPENR_NL_CPB;
-
-// Logical block of a launch of n blocks such that consecutive logical blocks
-// share an XCD (blocks b and b + 8 are dealt to one XCD, MI355X_MICROARCH
-// "Workgroup dispatch"): XCD x of the round-robin deal gets the contiguous
-// logical range [x*q + min(x, r), ...), q = n / 8, r = n % 8.  Speed only
-// (L2 locality), never correctness: every logical block is still run once.
-__device__ __forceinline__ uint32_t xcd_logical_block(uint32_t b, uint32_t n) {
-  const uint32_t x = b & 7u, i = b >> 3, qn = n >> 3, r = n & 7u;
-  return x * qn + min(x, r) + i;
-}
+constexpr uint32_t kNlChunksPerBlock = 2;
 
 // Byte-SIMD (SWAR) next-hop pass.  The compare of spf_nh_levels_kernel,
 // lvl(n, v) + 1 == lvl(s, v), costs ~8 VALU ops per (neighbour, node): at
@@ -3711,7 +3679,7 @@ __device__ __forceinline__ void nl_dist_from_levels(
   uint32_t* dw = a.dist_w + (size_t)q * a.Vp + v0;
   const uint32_t b[4] = {ls & 0xFFu, (ls >> 8) & 0xFFu, (ls >> 16) & 0xFFu, ls >> 24};
   if (v0 + 4 <= a.V && !swar_zero_bytes(~ls)) { // no byte is 255
-    nt_u32x4 w;
+    u32x4 w;
     if (a.scale == 1) { // hop count / metric 1: no multiplies (quarter-rate v_mul_lo)
       w.x = b[0];
       w.y = b[1];
@@ -3723,7 +3691,7 @@ __device__ __forceinline__ void nl_dist_from_levels(
       w.z = b[2] * a.scale;
       w.w = b[3] * a.scale;
     }
-    st_stream(reinterpret_cast<nt_u32x4*>(dw), w, a.nt_store != 0);
+    *reinterpret_cast<u32x4*>(dw) = w;
     return;
   }
 #pragma unroll
@@ -3873,7 +3841,7 @@ __device__ __forceinline__ void nl_swar_held(
       // node-major: node v0 + i, word w at (v0 + i) * Wm + w; narrow rows
       // (B < 8 bytes per node, one word) as one 4 / 8 / 16-byte run
       if (H <= 3 && B < 8) {
-        nh_store4_narrow(nhrow_b, B, v0, a.V, held[0], a.nt_store != 0);
+        nh_store4_narrow(nhrow_b, B, v0, a.V, held[0]);
       } else if (H <= 3 && v0 + 4 <= a.V) {
         ulonglong2* o = reinterpret_cast<ulonglong2*>(nhrow + (size_t)v0 * Wm);
         if (Wm == 1) {
@@ -4072,20 +4040,11 @@ __global__ __launch_bounds__(T) void spf_nh_levels_held_kernel(
   __shared__ uint32_t st_node[H * 64];
   __shared__ uint32_t st_nt[2 * H];
   // consecutive blocks: consecutive sources at the same chunk (neighbouring
-  // name ranks share neighbours, so their row reads meet in L2); with
-  // OPENR_NL_XCD=1 consecutive logical blocks also share an XCD
-  const uint32_t bid = a.xcd_swizzle ? xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
+  // name ranks share neighbours, so their row reads meet in L2)
+  const uint32_t bid = blockIdx.x;
   const uint32_t nsrc = H <= 3 ? a.nq : nmid;
-  uint32_t c = bid / nsrc;
-  uint32_t q = H <= 3 ? bid - c * nsrc : big[bid - c * nsrc];
-  if (H <= 3 && a.held_order) {
-    const uint32_t it = a.held_order[blockIdx.x];
-    if (it == kInf32) {
-      return;
-    }
-    q = it / a.held_nch;
-    c = it - q * a.held_nch;
-  }
+  const uint32_t c = bid / nsrc;
+  const uint32_t q = H <= 3 ? bid - c * nsrc : big[bid - c * nsrc];
   const uint32_t Wm = a.nh_w[q];
   if ((a.flags[0] & 1u) != 0 || Wm > H || (H > 3 && Wm <= 3)) {
     return;
@@ -4138,24 +4097,6 @@ struct NlV2Args {
   uint32_t nsolo, nsub;
   // bytes of the level table (< 2^31: the kernel's buffer descriptor)
   uint32_t lvl_bytes;
-  // measurement only (OPENR_NL_V2_DBG): bit 0 skips the solo items, bit 1 the
-  // groups, bit 2 computes without storing (the results stay live)
-  uint32_t dbg;
-  // block order (OPENR_NL_V2_ORDER): 0 = all solo items chunk-major, then
-  // all groups; 1 = chunk-major over both kinds (chunk c: its solo items,
-  // then its groups); 2 = order 1 with XCD-contiguous logical ranges, so an
-  // XCD sweeps ~1/8 of the chunks and the level-row slices its blocks read
-  // stay in its L2 (round-robin dealing makes every XCD fetch every row);
-  // 3 = chunk-major with the chunk's solo and group items interleaved in
-  // proportion, so VALU-heavy solo blocks and store-heavy group blocks are
-  // resident together; 4 = item-major; 5 = an explicit block map (xmap):
-  // items of one neighbour class (same largest neighbour: a pod's FSWs, a
-  // plane's SSWs, a pod's RSW groups) chunk by chunk, cut into 8 cost-
-  // balanced ranges, range x on the blocks b = 8 j + x that the dispatcher
-  // deals to XCD x, so a class's neighbour rows are fetched into one L2
-  uint32_t order;
-  const uint32_t* xmap = nullptr; // [nmap] item << 12 | chunk, ~0 = empty
-  uint32_t nmap = 0;
   // round 6: 2-bit level rows (spf_lvl_trit_kernel: level mod 3, 3 =
   // unreached; row stride tstride = Vp8 / 4 bytes).  An item whose sources
   // are all transit reads its NEIGHBOURS' rows in this form (a quarter of
@@ -4422,50 +4363,7 @@ __device__ __forceinline__ void nl_v2_solo(const NhLevelsArgs& a, const NlV2Args
   }
   const uint32_t v0 = vbase + 4 * lane;
   const bool active = v0 < a.V;
-  const uint8_t* lvl_v0 = a.lvl + v0;
   const nl_cptr<NlEnt> ent = nl_const(v.ent + d.lo);
-  if (v.dbg & 8u) {
-    // measurement: the pass's stores alone (same addresses, no loads)
-    if (!(v.dbg & 32u) && d.B >= 8 && !(v.dbg & 64u)) {
-      // wide masks through the LDS tile, as the pass stores them (every lane)
-      uint64_t hx[kNsHeldMax][4];
-#pragma unroll
-      for (uint32_t w = 0; w < kNsHeldMax; ++w) {
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-          hx[w][i] = v0 + i + w;
-        }
-      }
-      nl_store_wide(a.nhb + d.nhb_off, vbase, a.V, d.Wm, hx, tile, lane);
-      if (active && a.dist_w && !(v.dbg & 16u)) {
-        nl_dist_from_levels(a, d.q, v0, 0x01010101u * (v0 & 7u));
-      }
-      return;
-    }
-    if (!active) {
-      return;
-    }
-    uint64_t x4[4] = {v0, v0 + 1, v0 + 2, v0 + 3};
-    if (a.dist_w && !(v.dbg & 16u)) {
-      nl_dist_from_levels(a, d.q, v0, 0x01010101u * (v0 & 7u));
-    }
-    uint8_t* nb = a.nhb + d.nhb_off;
-    if (v.dbg & 32u) {
-    } else if (d.B < 8) {
-      nh_store4_narrow(nb, d.B, v0, a.V, x4);
-    } else if (v.dbg & 64u) { // the register-layout stores (before LDS staging)
-      uint64_t* nr = reinterpret_cast<uint64_t*>(nb);
-      for (uint32_t w = 0; w < d.Wm; ++w) {
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-          if (v0 + i < a.V) {
-            nr[(size_t)(v0 + i) * d.Wm + w] = x4[i];
-          }
-        }
-      }
-    }
-    return;
-  }
   // drained neighbours: lane j tests entry 64w + j (every lane takes part)
   uint64_t ntm[kNsHeldMax];
 #pragma unroll
@@ -4537,18 +4435,8 @@ __device__ __forceinline__ void nl_v2_solo(const NhLevelsArgs& a, const NlV2Args
       }
     }
   }
-  if (v.dbg & 4u) {
-    uint64_t x = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kNsHeldMax; ++w) {
-      x ^= held[w][0] ^ held[w][1] ^ held[w][2] ^ held[w][3];
-    }
-    if (x != 0x5A5A5A5A12345678ull) {
-      return; // measurement: no stores
-    }
-  }
   uint8_t* nhrow_b = a.nhb + d.nhb_off;
-  if (d.B >= 8 && !(v.dbg & 64u)) {
+  if (d.B >= 8) {
     nl_store_wide(nhrow_b, vbase, a.V, d.Wm, held, tile, lane); // every lane
     if (active && a.dist_w) {
       nl_dist_from_levels(a, d.q, v0, ls);
@@ -4564,7 +4452,7 @@ __device__ __forceinline__ void nl_v2_solo(const NhLevelsArgs& a, const NlV2Args
   uint64_t* nhrow = reinterpret_cast<uint64_t*>(nhrow_b);
   const uint32_t Wm = d.Wm;
   if (d.B < 8) {
-    nh_store4_narrow(nhrow_b, d.B, v0, a.V, held[0], a.nt_store != 0);
+    nh_store4_narrow(nhrow_b, d.B, v0, a.V, held[0]);
   } else if (v0 + 4 <= a.V) {
     ulonglong2* o = reinterpret_cast<ulonglong2*>(nhrow + (size_t)v0 * Wm);
     if (Wm == 1) {
@@ -4611,30 +4499,8 @@ __device__ __forceinline__ void nl_v2_group(const NhLevelsArgs& a, const NlV2Arg
   }
   const uint32_t v0 = vbase + 4 * lane;
   const bool active = v0 < a.V;
-  const uint8_t* lvl_v0 = a.lvl + v0;
   const nl_cptr<NlEnt> ent = nl_const(v.ent + d.lo);
   const nl_cptr<NlMem> mem = nl_const(v.mem + d.m0);
-  if (v.dbg & 8u) {
-    // measurement: the group's stores alone (same addresses, no loads)
-    if (!active) {
-      return;
-    }
-    for (uint32_t i = 0; i < d.cnt; ++i) {
-      const NlMem m{mem[i].q, 0u, mem[i].nhb_off};
-      uint8_t* row = a.nhb + m.nhb_off;
-      if (v0 + 4 <= a.V && !(v.dbg & 32u)) {
-        if (d.B == 1) {
-          *reinterpret_cast<uint32_t*>(row + v0) = v0;
-        } else {
-          *reinterpret_cast<nt_u32x2*>(row + 2 * (size_t)v0) = nt_u32x2{v0, v0};
-        }
-      }
-      if (a.dist_w && !(v.dbg & 16u)) {
-        nl_dist_from_levels(a, m.q, v0, 0x01010101u * (v0 & 7u));
-      }
-    }
-    return;
-  }
   bool nt = false;
   if (lane < d.n) {
     nt = !nl_transit(a.trbits, ent[lane].node);
@@ -4757,17 +4623,14 @@ __device__ __forceinline__ void nl_v2_group(const NhLevelsArgs& a, const NlV2Arg
       }
       uint8_t* row = a.nhb + __builtin_amdgcn_readfirstlane((uint32_t)mem[i].nhb_off) +
                      ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(mem[i].nhb_off >> 32)) << 32);
-      if ((v.dbg & 4u) && (P0 ^ P1) != 0x5A5A5A5Au) {
-        continue; // measurement: no stores
-      }
       if (v0 + 4 <= a.V) {
         if (d.B == 1) {
-          st_stream(reinterpret_cast<uint32_t*>(row + v0), P0, a.nt_store != 0);
+          *reinterpret_cast<uint32_t*>(row + v0) = P0;
         } else {
-          nt_u32x2 w2;
+          u32x2 w2;
           w2.x = __builtin_amdgcn_perm(P1, P0, 0x05010400u); // nodes 0, 1 (16 bits each)
           w2.y = __builtin_amdgcn_perm(P1, P0, 0x07030602u); // nodes 2, 3
-          st_stream(reinterpret_cast<nt_u32x2*>(row + 2 * (size_t)v0), w2, a.nt_store != 0);
+          *reinterpret_cast<u32x2*>(row + 2 * (size_t)v0) = w2;
         }
       } else {
 #pragma unroll
@@ -4785,10 +4648,10 @@ __device__ __forceinline__ void nl_v2_group(const NhLevelsArgs& a, const NlV2Arg
   }
 }
 
-// blocks [0, nsolo * nch): solo (source, chunk) items, chunk-major (the
-// heavy SSW / FSW sources of the fabric first); then the groups' (sub-group,
-// chunk) items.  A BFS deeper than 254 levels leaves everything to
-// spf_nh_levels_swar_kernel.
+// One block per (item, chunk), item-major; the group items are spread evenly
+// among the solo items, so VALU-heavy solo blocks and store-heavy group
+// blocks are resident together.  A BFS deeper than 254 levels leaves
+// everything to spf_nh_levels_swar_kernel.
 // TRITS: the instance with the 2-bit neighbour-row path compiled in
 // (OPENR_NL_TRIT=1); the default instance carries the byte path alone
 template <uint32_t T, bool TRITS>
@@ -4851,57 +4714,19 @@ __global__ __launch_bounds__(T) void spf_nh_levels_v2_kernel(NhLevelsArgs a, NlV
       nl_v2_group<T, false, false>(a, v, k, c, rs, rt);
     }
   };
-  if (v.order == 5) {
-    const uint32_t e = v.xmap[blockIdx.x];
-    if (e == kInf32) {
-      return; // padding of a shorter XCD range
-    }
-    const uint32_t k = e >> 12, c = e & 0xFFFu;
-    if (k < v.nsolo) {
-      nl_v2_solo_t(k, c);
-    } else {
-      nl_v2_group_t(k - v.nsolo, c);
-    }
-    return;
-  }
-  if (v.order != 0) {
-    const uint32_t bid = v.order == 2 ? xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
-    const uint32_t per = v.nsolo + v.nsub;
-    uint32_t c = bid / per, k = bid - c * per;
-    if (v.order == 4) { // item-major: an item's chunks back to back
-      const uint32_t nch = (a.V + 4 * T - 1) / (4 * T);
-      k = bid / nch;
-      c = bid - k * nch;
-    }
-    if (v.order >= 3) {
-      // Bresenham spread of the nsub group items over the chunk's items
-      const uint32_t gi = (uint32_t)((uint64_t)k * v.nsub / per);
-      const bool grp = (uint32_t)((uint64_t)(k + 1) * v.nsub / per) > gi;
-      k = grp ? v.nsolo + gi : k - gi;
-    }
-    if (k < v.nsolo) {
-      if (!(v.dbg & 1u)) {
-        nl_v2_solo_t(k, c);
-      }
-    } else if (!(v.dbg & 2u)) {
-      nl_v2_group_t(k - v.nsolo, c);
-    }
-    return;
-  }
-  const uint32_t bid = blockIdx.x;
-  const uint32_t ns = v.nsolo * ((a.V + 4 * T - 1) / (4 * T));
-  if (bid < ns) {
-    if (v.dbg & 1u) {
-      return;
-    }
-    const uint32_t c = bid / v.nsolo;
-    nl_v2_solo_t(bid - c * v.nsolo, c);
+  // item-major: an item's chunks back to back
+  const uint32_t nch = (a.V + 4 * T - 1) / (4 * T);
+  uint32_t k = blockIdx.x / nch;
+  const uint32_t c = blockIdx.x - k * nch;
+  // Bresenham spread of the nsub group items over the items
+  const uint32_t per = v.nsolo + v.nsub;
+  const uint32_t gi = (uint32_t)((uint64_t)k * v.nsub / per);
+  const bool grp = (uint32_t)((uint64_t)(k + 1) * v.nsub / per) > gi;
+  k = grp ? v.nsolo + gi : k - gi;
+  if (k < v.nsolo) {
+    nl_v2_solo_t(k, c);
   } else {
-    if (v.dbg & 2u) {
-      return;
-    }
-    const uint32_t b2 = bid - ns, c = b2 / v.nsub;
-    nl_v2_group_t(b2 - c * v.nsub, c);
+    nl_v2_group_t(k - v.nsolo, c);
   }
 }
 
@@ -5060,13 +4885,8 @@ void spf_nh_levels_kernel(NhLevelsArgs a) {
   __shared__ uint32_t st_row[kNlStage];
   __shared__ uint32_t st_node[kNlStage];
   const uint32_t nchunks = (a.V + kNlChunk - 1) / kNlChunk;
-  // sources of one pod / plane are adjacent name ranks and share neighbours:
-  // run them on one XCD so its L2 serves their neighbours' level rows (the
-  // 8 FSWs of a pod all read its 48 RSW rows; dealt round-robin they fetched
-  // each RSW row once per XCD)
-  const uint32_t bid = a.xcd_swizzle ? xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
-  const uint32_t cb = bid / a.nq;
-  const uint32_t q = bid - cb * a.nq;
+  const uint32_t cb = blockIdx.x / a.nq;
+  const uint32_t q = blockIdx.x - cb * a.nq;
   const uint32_t s = a.src[q];
   const uint32_t c0 = cb * kNlChunksPerBlock;
   const uint32_t c1 = min(nchunks, c0 + kNlChunksPerBlock);
@@ -5086,9 +4906,9 @@ void spf_nh_levels_kernel(NhLevelsArgs a) {
       nl_body_multi_staged<false>(a, q, s, c0, c1, st_row, st_node);
     } else if (wm == 1) {
       nl_body_multi<false, 1>(a, q, s, c0, c1, st_row, st_node);
-    } else if (wm == 2 && a.held_words) {
+    } else if (wm == 2) {
       nl_body_multi<false, 2>(a, q, s, c0, c1, st_row, st_node);
-    } else if (wm == 3 && a.held_words) {
+    } else if (wm == 3) {
       nl_body_multi<false, 3>(a, q, s, c0, c1, st_row, st_node);
     } else {
       nl_body_multi<false, 0>(a, q, s, c0, c1, st_row, st_node);
@@ -7404,10 +7224,6 @@ struct TraceHeavyArgs {
   // OPENR_SPF_TRACE_STATS=1: per heavy query {wall ticks (100 MHz), steps,
   // pushes, global batch loads}; nullptr = off
   unsigned long long* hstat;
-  // blocks of query hi built on XCD hi % 8, the XCD its DFS block runs on
-  // (blocks go round-robin over the 8 XCDs): its arena is read from that
-  // XCD's L2 instead of across the fabric.  0: plain item order.
-  uint32_t xcd;
   uint32_t L;         // link ids (the removed-link bitset of the reach kernel)
   uint32_t* fq;       // [nh][2][V] the reach kernel's BFS frontiers
   const uint32_t* nodes; // [V] build order: in-degree <= 16 first (nsmall), then the rest
@@ -7437,15 +7253,12 @@ __global__ __launch_bounds__(64 * kHvWaves) void spf_trace_heavy_build_kernel(Tr
   const uint32_t nbig = H.V - H.nsmall;
   const uint32_t bs = (H.nsmall + 4 * kHvWaves - 1) / (4 * kHvWaves);
   const uint32_t bq = hv_blocks(H.nsmall, nbig);
-  uint32_t hi, k;
-  if (H.xcd) {
-    const uint32_t ka = blockIdx.x >> 3;
-    hi = (ka / bq) * 8u + (blockIdx.x & 7u);
-    k = ka % bq;
-  } else {
-    hi = blockIdx.x / bq;
-    k = blockIdx.x % bq;
-  }
+  // blocks of query hi are built on XCD hi % 8, the XCD its DFS block runs on
+  // (blocks go round-robin over the 8 XCDs): its arena is read from that
+  // XCD's L2 instead of across the fabric
+  const uint32_t ka = blockIdx.x >> 3;
+  const uint32_t hi = (ka / bq) * 8u + (blockIdx.x & 7u);
+  const uint32_t k = ka % bq;
   if (hi >= H.nh) {
     return; // whole block
   }
@@ -8311,7 +8124,6 @@ struct spf_query {
   uint32_t ms_nfw = 0, ms_nbatch = 0;
   uint32_t dstep_shift = 5; // delta-stepping bucket width 2^shift
   bool dstep_lbk = false;    // bucket bytes in LDS (else from the dist row)
-  uint32_t dstep_bs = 1024;  // delta-stepping workgroup size
   uint32_t dstep_fshift = 5; // bucket-byte resolution (dstep_tune)
   uint32_t dstep_noret = 0;  // relaxation mode bits (dstep_tune)
   uint32_t dstep_pack = 0;   // packed out-edges: 0 off, 1 scalar, 2 vector
@@ -8377,6 +8189,7 @@ struct spf_query {
   bool narrow = false, nh_direct = false;
   bool screen_direct = false; // the last screen wrote its copies narrowed (run_screen)
   bool nl_swar = true; // the byte-SIMD next-hop kernels (OPENR_NL_SWAR, read at creation)
+  bool ms_lvl_only = true; // distances from the level rows (OPENR_MS_LVL_ONLY, read at creation)
   uint8_t* d_nhb = nullptr;
   uint64_t* d_nhb_off = nullptr;
   uint32_t* d_nh_b = nullptr;
@@ -8399,7 +8212,6 @@ struct spf_query {
   uint32_t* d_qctr = nullptr; // dstep source-claim counter
   uint32_t* d_wl = nullptr;   // repair work list (spf_whatif_worklist_kernel)
   uint32_t* d_big = nullptr;  // nh_levels: queries with more than kNsHeldMax mask words
-  uint32_t* d_held_order = nullptr; // OPENR_NL_ORDER=1: XCD-contiguous held-kernel work order
   // the v2 next-hop pass (spf_nh_levels_v2_kernel, OPENR_NL_V2): solo / group
   // descriptors, members and neighbour entries in one pooled block, valid
   // while the graph's neighbour lists are those of nbr_gen
@@ -8409,7 +8221,6 @@ struct spf_query {
   NlV2Args v2{};
   bool has_v2 = false;
   uint64_t v2_gen = 0;
-  uint32_t held_blocks = 0, held_nch = 0, held_t = 0;
   uint32_t nbig = 0;
   uint32_t nmid = 0;          // the first nmid of them have at most kNsHeldWide words
   // zero-metric plan (spf_zvar_kernel): variant tables, their closure pairs
@@ -8689,61 +8500,6 @@ int build_nl_v2(spf_query* q, const uint32_t* sources, const std::vector<int32_t
   if ((uint64_t)(solo.size() + subs.size()) * nch > 0x7FFFFFFFull) {
     return SPF_OK; // the held kernel's own limit check reports it
   }
-  const uint32_t vorder = std::min<uint32_t>(5, env_u32("OPENR_NL_V2_ORDER", 4));
-  std::vector<uint32_t> xmap;
-  if (vorder == 5 && solo.size() + subs.size() < (1u << 20) && nch <= 4096) {
-    // items by neighbour class (largest neighbour id), chunk by chunk within
-    // a class; cost ~ the neighbour rows a block reads plus its outputs
-    struct It {
-      uint32_t key, k, cost;
-    };
-    std::vector<It> items;
-    for (uint32_t k = 0; k < solo.size(); ++k) {
-      const uint32_t s = sources[solo[k].q];
-      items.push_back({g->nbrs[g->nbr_off[s + 1] - 1], k, 4 + solo[k].n + 2 * solo[k].B});
-    }
-    for (uint32_t j = 0; j < subs.size(); ++j) {
-      const NlSub& sb = subs[j];
-      items.push_back({ent[sb.lo + sb.n - 1].node, (uint32_t)solo.size() + j, 4 + sb.n + 2 * sb.cnt});
-    }
-    std::stable_sort(items.begin(), items.end(), [](const It& x, const It& y) { return x.key < y.key; });
-    std::vector<uint32_t> blocks;
-    std::vector<uint64_t> cost;
-    for (size_t i = 0; i < items.size();) {
-      size_t j = i;
-      while (j < items.size() && items[j].key == items[i].key) {
-        ++j;
-      }
-      for (uint32_t c = 0; c < nch; ++c) {
-        for (size_t x = i; x < j; ++x) {
-          blocks.push_back(items[x].k << 12 | c);
-          cost.push_back(items[x].cost);
-        }
-      }
-      i = j;
-    }
-    uint64_t total = 0;
-    for (uint64_t c : cost) {
-      total += c;
-    }
-    std::vector<std::vector<uint32_t>> rng(8);
-    uint64_t acc = 0;
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      const uint32_t x = (uint32_t)std::min<uint64_t>(7, acc * 8 / std::max<uint64_t>(total, 1));
-      rng[x].push_back(blocks[i]);
-      acc += cost[i];
-    }
-    size_t mx = 0;
-    for (const auto& r : rng) {
-      mx = std::max(mx, r.size());
-    }
-    xmap.assign(8 * mx, kInf32);
-    for (uint32_t x = 0; x < 8; ++x) {
-      for (size_t j = 0; j < rng[x].size(); ++j) {
-        xmap[8 * j + x] = rng[x][j];
-      }
-    }
-  }
   const uint64_t lvl_bytes = (uint64_t)q->nrows * q->Vp8;
   if (lvl_bytes >= 0x80000000ull) {
     return SPF_OK; // beyond one buffer descriptor: the held kernel
@@ -8756,10 +8512,8 @@ int build_nl_v2(spf_query* q, const uint32_t* sources, const std::vector<int32_t
   const size_t o_solo = 0, o_sub = al(o_solo + solo.size() * sizeof(NlSolo)),
                o_mem = al(o_sub + subs.size() * sizeof(NlSub)),
                o_ent = al(o_mem + mem.size() * sizeof(NlMem)),
-               o_map = al(o_ent + ent.size() * sizeof(NlEnt)),
-               total = al(o_map + xmap.size() * 4);
+               total = al(o_ent + ent.size() * sizeof(NlEnt));
   std::vector<uint8_t> host(total, 0);
-  std::memcpy(host.data() + o_map, xmap.data(), xmap.size() * 4);
   std::memcpy(host.data() + o_solo, solo.data(), solo.size() * sizeof(NlSolo));
   std::memcpy(host.data() + o_sub, subs.data(), subs.size() * sizeof(NlSub));
   std::memcpy(host.data() + o_mem, mem.data(), mem.size() * sizeof(NlMem));
@@ -8776,13 +8530,7 @@ int build_nl_v2(spf_query* q, const uint32_t* sources, const std::vector<int32_t
   q->v2.nsolo = (uint32_t)solo.size();
   q->v2.nsub = (uint32_t)subs.size();
   q->v2.lvl_bytes = (uint32_t)lvl_bytes;
-  q->v2.dbg = env_u32("OPENR_NL_V2_DBG", 0);
   q->v2.shallow = env_flag("OPENR_NL_SHALLOW", 1) ? 1u : 0u;
-  // item-major (4): measured fastest with the LDS-staged wide tiles
-  // (profiles/r05k: 0.364 ms against 0.385-0.389 for the chunk-major orders)
-  q->v2.order = vorder == 5 && xmap.empty() ? 4u : vorder;
-  q->v2.xmap = reinterpret_cast<const uint32_t*>(b + o_map);
-  q->v2.nmap = (uint32_t)xmap.size();
   // 2-bit neighbour rows (OPENR_NL_TRIT=1, opt-in): exact when every
   // half-edge is paired with an up reverse (uniform metric is the plan's
   // own condition), checked here since spf_graph_set_edges bumps nbr_gen and
@@ -9160,7 +8908,7 @@ void free_query(spf_query* q) {
         (void*)q->d_lvl, (void*)q->d_flags, (void*)q->d_perm,
         (void*)q->d_slab, (void*)q->d_msd, (void*)q->d_base_of,
         (void*)q->d_skip, (void*)q->d_key, (void*)q->d_qctr, (void*)q->d_wl, (void*)q->d_scatter,
-        (void*)q->d_trace, (void*)q->d_big, (void*)q->d_held_order, (void*)q->d_zl,
+        (void*)q->d_trace, (void*)q->d_big, (void*)q->d_zl,
         (void*)q->d_zvar, (void*)q->d_ms_mask, (void*)q->d_ms_flag,
         (void*)q->d_ovf, q->narrow ? (void*)q->d_nhb : nullptr, (void*)q->d_tcs, q->d_v2,
         (void*)q->d_trit,
@@ -9877,8 +9625,8 @@ uint32_t dstep_bucket_shift(const spf_graph* g, bool want_nh) {
   if (!want_nh) {
     shift += 2;
   }
-  if (const char* env = getenv("OPENR_SPF_DSTEP_SHIFT")) {
-    shift = (uint32_t)std::min(24, std::max(0, atoi(env)));
+  if (const int env = env_dstep_shift(); env >= 0) {
+    shift = (uint32_t)env;
   }
   return shift;
 }
@@ -9923,9 +9671,6 @@ uint64_t graph_ecc(spf_graph* g) {
 // down to the resolution that still spreads 1.25x one node's eccentricity
 // over the 254 byte values (saturation is exact, only slower); relaxations gather d[v] coherently and issue
 // non-returning atomicMin; out-edges are read as packed 16-byte chunks.
-// OPENR_SPF_DSTEP_FINE (byte bits below the bucket width), _NORET (bit 0
-// non-returning atomics, bit 1 coherent gathers) and _PACK (0 off, 1 scalar,
-// 2 vector) override.
 void dstep_tune(spf_graph* g, spf_query* q, bool push_only) {
   q->dstep_fshift = q->dstep_shift;
   q->dstep_noret = 0;
@@ -9933,8 +9678,8 @@ void dstep_tune(spf_graph* g, spf_query* q, bool push_only) {
   if (!push_only || !q->dstep_lbk) {
     return;
   }
-  uint32_t fine = 4;
-  if (getenv("OPENR_SPF_DSTEP_SHIFT") == nullptr) {
+  const uint32_t fine = 4; // byte bits below the bucket width
+  if (env_dstep_shift() < 0) {
     q->dstep_shift += 1;
   }
   const uint64_t span = graph_ecc(g) + graph_ecc(g) / 4;
@@ -9942,21 +9687,12 @@ void dstep_tune(spf_graph* g, spf_query* q, bool push_only) {
   while (fs < q->dstep_shift && (span >> fs) > 250) {
     ++fs;
   }
-  if (const char* env = getenv("OPENR_SPF_DSTEP_FINE")) {
-    fine = (uint32_t)std::max(0, atoi(env));
-    fs = q->dstep_shift - std::min(fine, q->dstep_shift);
-  }
   q->dstep_fshift = fs;
-  // bits 2-3 (bytes lowered at relaxation time, no gather into unreached
-  // nodes): 14.9 -> 14.0 us/SPF on the 100k WAN (profiles/quick_wan.py)
+  // bit 0 non-returning atomics, bit 1 coherent gathers, bits 2-3 (bytes
+  // lowered at relaxation time, no gather into unreached nodes): 14.9 ->
+  // 14.0 us/SPF on the 100k WAN (profiles/quick_wan.py)
   q->dstep_noret = 15;
-  if (const char* env = getenv("OPENR_SPF_DSTEP_NORET")) {
-    q->dstep_noret = (uint32_t)std::max(0, std::min(15, atoi(env)));
-  }
   q->dstep_pack = g->cw_bits ? 2 : 0;
-  if (const char* env = getenv("OPENR_SPF_DSTEP_PACK")) {
-    q->dstep_pack = g->cw_bits ? (uint32_t)std::max(0, std::min(2, atoi(env))) : 0;
-  }
 }
 
 // bucket width for spf_msdstep_kernel: the eccentricity of one source (host
@@ -9994,8 +9730,8 @@ uint32_t msd_shift(const spf_graph* g, uint32_t s0) {
   while (shift < 24 && ((ecc >> shift) > 200 || (double)(2u << shift) <= delta)) {
     ++shift;
   }
-  if (const char* env = getenv("OPENR_SPF_MSD_SHIFT")) {
-    shift = (uint32_t)std::min(24, std::max(0, atoi(env)));
+  if (const int env = env_clamped("OPENR_SPF_MSD_SHIFT", 24); env >= 0) {
+    shift = (uint32_t)env;
   }
   return shift;
 }
@@ -10687,9 +10423,8 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
   // metrics that wrap (negative i32 as uint64): the literal DijkstraQ
   // replay; metric 0 / sums past 32 bits / a settle order: the wide plan
   // (OPENR_SPF_LITERAL=1 forces the replay on any 64-bit graph: measurement)
-  const char* lit_env = getenv("OPENR_SPF_LITERAL");
   const bool literal =
-      (g->wrap && !unit) || (g->exact && !unit && lit_env && atoi(lit_env) == 1);
+      (g->wrap && !unit) || (g->exact && !unit && env_int("OPENR_SPF_LITERAL", 0) == 1);
   // metric-0 links on an otherwise uniform metric: MS-BFS variant tables
   // (spf_zvar_kernel) instead of the wide plan (OPENR_SPF_ZERO_MSBFS=0: wide)
   std::vector<ZeroLink> zlinks;
@@ -10697,7 +10432,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
   const bool zcand = !unit && !literal && !want_order && !has_ign && g->exact && g->n_zero &&
                      nq >= 32 && V <= kMsThreads * kMsMaxK && 2 * (size_t)V * 4 <= kLdsLimit &&
                      env_flag("OPENR_SPF_ZERO_MSBFS", 1) &&
-                     !(getenv("OPENR_SPF_MSBFS") && atoi(getenv("OPENR_SPF_MSBFS")) == 0) &&
+                     env_msbfs_width() != 0 &&
                      zero_plan_links(g, zlinks, zc);
   const bool exact = ((g->exact && !unit) || want_order) && !zcand;
   const bool uniform = unit || g->uniform != 0 || zcand;
@@ -10731,7 +10466,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
     const bool msbfs_candidate = !rows_ok && uniform && !literal &&
                                  V <= kMsThreads * kMsMaxK &&
                                  2 * (size_t)V * 4 <= kLdsLimit &&
-                                 !(getenv("OPENR_SPF_MSBFS") && atoi(getenv("OPENR_SPF_MSBFS")) == 0) &&
+                                 env_msbfs_width() != 0 &&
                                  env_flag("OPENR_SPF_MSBFS_HELPERS", 1);
     if (msbfs_candidate) {
       // no bound on the helper count: it is < V, and one MS-BFS pass over
@@ -10772,7 +10507,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
     if (!rows_ok && !uniform && !literal && V >= 4096 && V <= 65535 &&
         lds_ctl_bytes(g, 0) + lds_state_bytes(V) <= kLdsLimit && maxw <= 16 &&
         (size_t)nq * 16 <= (size_t)g->num_cus && g->cw_bits && g->maxw <= kDlMaxDist &&
-        env_flag("OPENR_SPF_FEW_DSTEP", 1) && getenv("OPENR_SPF_DSTEP") == nullptr &&
+        env_flag("OPENR_SPF_FEW_DSTEP", 1) && !env_dstep_off() &&
         env_flag("OPENR_SPF_DSTEP_LDSROW", 1) && env_flag("OPENR_SPF_FEW_ROWS", 1)) {
       std::vector<uint32_t> extra;
       for (uint32_t i = 0; i < nq; ++i) {
@@ -10817,8 +10552,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
     // 25 KB image, 2 workgroups per CU — measured slower on the 100k WAN:
     // the second 400 KB row per CU and the per-phase row reads of pending
     // nodes cost more than the extra waves hide)
-    const char* lbk_env = getenv("OPENR_SPF_DSTEP_LDSBKT");
-    q->dstep_lbk = !(lbk_env && atoi(lbk_env) == 0);
+    q->dstep_lbk = env_flag("OPENR_SPF_DSTEP_LDSBKT", 1);
     q->dstep_ign_cap = has_ign ? std::min(max_ign, kIgnLdsMax) : 0; // sorted list only
     const size_t dstep_lds =
         (2 * (size_t)g->nbw + kCtlWords + q->dstep_ign_cap) * 4 +
@@ -10830,14 +10564,13 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
     const bool few = !big && !has_ign && V >= 4096 && (size_t)nq * 16 <= (size_t)g->num_cus &&
                      env_flag("OPENR_SPF_FEW_DSTEP", 1);
     const bool dstep = (big || few) && !uniform && dstep_lds <= kLdsLimit && maxw <= 16 &&
-                       getenv("OPENR_SPF_DSTEP") == nullptr;
+                       !env_dstep_off();
     // many distance-only rows of such a graph: 32 sources per workgroup over
     // a node-major slab.  Measured slower than per-source delta-stepping on
     // the 100k WAN (0.145 vs 0.100 ms/SPF at 8192 sources: the 12.8 MB slab
     // per workgroup does not stay on chip), so opt-in: OPENR_SPF_MSD=1.
-    const char* msd_env = getenv("OPENR_SPF_MSD");
     const bool msd = big && !uniform && !want_nh && !has_ign && nq >= 2 * kMsdK &&
-                     msd_lds_bytes(g) <= kLdsLimit && msd_env && atoi(msd_env) == 1;
+                     msd_lds_bytes(g) <= kLdsLimit && env_int("OPENR_SPF_MSD", 0) == 1;
     if (dstep && q->nh == NhPlan::Rows && !few_rows) {
       q->nh = NhPlan::Inline;
     }
@@ -10854,8 +10587,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
       q->wmax = 0;
       q->lds_bytes = msd_lds_bytes(g);
       q->dstep_shift = msd_shift(g, desc->sources[0]);
-      const char* cl = getenv("OPENR_SPF_MSD_CLUSTER");
-      msd_perm = msd_batches(g, desc->sources, nq, !(cl && atoi(cl) == 0));
+      msd_perm = msd_batches(g, desc->sources, nq, env_flag("OPENR_SPF_MSD_CLUSTER", 1));
       q->msd_nbatch = (uint32_t)(msd_perm.size() / kMsdK);
       q->grid = std::min<uint32_t>(q->msd_nbatch, (uint32_t)g->num_cus);
     } else if (V <= 65535 && lds <= kLdsLimit && !(few && dstep) && !few_rows) {
@@ -10872,14 +10604,9 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
       // Delta = Theta(w/d)), a power of two; OPENR_SPF_DSTEP_SHIFT overrides
       q->dstep_shift = dstep_bucket_shift(g, want_nh);
       dstep_tune(g, q, !want_nh);
-      const char* bs_env = getenv("OPENR_SPF_DSTEP_BS");
-      q->dstep_bs = (bs_env && atoi(bs_env) == 512) ? 512 : 1024;
       // workgroups per CU: 2048 threads per CU, LDS permitting
-      uint32_t per_cu = (uint32_t)std::max<size_t>(
-          1, std::min<size_t>(2048 / q->dstep_bs, kLdsLimit / std::max<size_t>(dstep_lds, 1)));
-      if (const char* pc = getenv("OPENR_SPF_DSTEP_PERCU")) {
-        per_cu = std::max<uint32_t>(1, std::min<uint32_t>(per_cu, (uint32_t)atoi(pc)));
-      }
+      const uint32_t per_cu = (uint32_t)std::max<size_t>(
+          1, std::min<size_t>(2048 / kDstepThreads, kLdsLimit / std::max<size_t>(dstep_lds, 1)));
       const uint32_t nr = nq + (uint32_t)helpers.size();
       q->grid = std::min<uint32_t>(std::max<uint32_t>(nr, 1), (uint32_t)g->num_cus * per_cu);
       // distance rows whose every value fits 12 bits (metrics <= 4,094; the
@@ -10896,8 +10623,8 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
         // buckets mean fewer phases (100k WAN, profiles/r04c: 2^4 9.5,
         // 2^5 7.7, 2^7 6.7 us/SPF)
         q->dlds_shift = std::min<uint32_t>(dstep_bucket_shift(g, false) + 1, 11);
-        if (const char* env = getenv("OPENR_SPF_DSTEP_LSHIFT")) {
-          q->dlds_shift = (uint32_t)std::min(11, std::max(0, atoi(env)));
+        if (const int env = env_clamped("OPENR_SPF_DSTEP_LSHIFT", 11); env >= 0) {
+          q->dlds_shift = (uint32_t)env;
         }
       }
     } else if (ctl <= kLdsLimit) {
@@ -10920,7 +10647,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
       V <= kMsThreads * kMsMaxK && helpers.empty() &&
       (q->dist == DistPlan::SsspLds || q->dist == DistPlan::SsspGmem) &&
       env_flag("OPENR_SPF_MSBFS_IGN", 1) &&
-      !(getenv("OPENR_SPF_MSBFS") && atoi(getenv("OPENR_SPF_MSBFS")) == 0) &&
+      env_msbfs_width() != 0 &&
       (uint64_t)((nq + 63) / 64) * g->E * 8 <= (1ull << 30)) {
     ms_ign_prev = q->dist;
     q->dist = DistPlan::BfsLds; // becomes MS-BFS just below
@@ -10930,8 +10657,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
   // (OPENR_SPF_MSBFS=0 disables, =32 / =64 picks the batch width)
   if ((q->dist == DistPlan::BfsLds || q->dist == DistPlan::BfsGmem) &&
       V <= kMsThreads * kMsMaxK && (nq + helpers.size() >= 32 || !helpers.empty())) {
-    const char* env = getenv("OPENR_SPF_MSBFS");
-    int width = env ? atoi(env) : 64;
+    int width = env_msbfs_width();
     if (width == 64 && 2 * (size_t)V * 8 > kLdsLimit) {
       width = 32; // the 64-bit frontier double buffer does not fit LDS
     }
@@ -11106,58 +10832,9 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
     if (!big.empty() && dev_upload_q(&q->d_big, big.data(), big.size()) != SPF_OK) {
       return bail(fail(SPF_E_NOMEM, "next-hop source list"));
     }
-    if (q->zvars == 0 && env_flag("OPENR_NL_V2", 1) && env_u32("OPENR_NL_ORDER", 0) != 1) {
+    if (q->zvars == 0 && env_flag("OPENR_NL_V2", 1)) {
       if (const int s = build_nl_v2(q, desc->sources, row_of); s != SPF_OK) {
         return bail(s);
-      }
-    }
-    // OPENR_NL_ORDER=1: the held kernel's (source, chunk) items cut into 8
-    // contiguous source ranges of equal cost (8 + neighbours per item), one
-    // per XCD (hardware block b runs on XCD b % 8), source-major inside a
-    // range: the rows an XCD's resident blocks read (a pod's RSW / FSW rows)
-    // stay in its L2 instead of every XCD fetching nearly every row
-    if (env_u32("OPENR_NL_ORDER", 0) == 1) {
-      const uint32_t ht = env_u32("OPENR_NL_HT", 256);
-      const uint32_t T = ht == 1024 ? 1024u : (ht == 512 ? 512u : 256u);
-      const uint32_t nch = (V + 4 * T - 1) / (4 * T);
-      double total = 0;
-      for (uint32_t i = 0; i < nq; ++i) {
-        if (q->nh_w[i] <= kNsHeldMax) {
-          const uint32_t s = desc->sources[i];
-          total += (double)nch * (8.0 + (g->nbr_off[s + 1] - g->nbr_off[s]));
-        }
-      }
-      std::vector<std::vector<uint32_t>> lists(8);
-      double acc = 0;
-      for (uint32_t i = 0; i < nq; ++i) {
-        if (q->nh_w[i] > kNsHeldMax) {
-          continue;
-        }
-        const uint32_t s = desc->sources[i];
-        const double cst = (double)nch * (8.0 + (g->nbr_off[s + 1] - g->nbr_off[s]));
-        const uint32_t x = std::min<uint32_t>(7, (uint32_t)(8.0 * (acc + 0.5 * cst) / total));
-        acc += cst;
-        for (uint32_t c = 0; c < nch; ++c) {
-          lists[x].push_back(i * nch + c);
-        }
-      }
-      size_t maxlen = 0;
-      for (const auto& l : lists) {
-        maxlen = std::max(maxlen, l.size());
-      }
-      std::vector<uint32_t> order(8 * maxlen, kInf32);
-      for (uint32_t x = 0; x < 8; ++x) {
-        for (size_t i = 0; i < lists[x].size(); ++i) {
-          order[i * 8 + x] = lists[x][i];
-        }
-      }
-      if (!order.empty() && nq * (uint64_t)nch < 0xFFFFFFFFull) {
-        if (dev_upload_q(&q->d_held_order, order.data(), order.size()) != SPF_OK) {
-          return bail(fail(SPF_E_NOMEM, "next-hop work order"));
-        }
-        q->held_blocks = (uint32_t)order.size();
-        q->held_nch = nch;
-        q->held_t = T;
       }
     }
   }
@@ -11183,6 +10860,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
   if (want_nh) {
     // the SWAR next-hop kernels write the output layout themselves
     q->nl_swar = env_flag("OPENR_NL_SWAR", 1) || q->zvars;
+    q->ms_lvl_only = env_flag("OPENR_MS_LVL_ONLY", 1) != 0;
     q->nh_direct = q->dist == DistPlan::MsBfs && q->nh == NhPlan::Levels && q->nl_swar;
     if (!q->narrow) {
       if (q->nh_total && pool_malloc((void**)&q->d_nh, q->nh_total * 8) != hipSuccess) {
@@ -11239,8 +10917,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
   // ignore lists on the fast plans run one baseline SPF per distinct source
   // first; queries whose ignored links are all off the baseline's shortest
   // path DAG copy its rows instead of running
-  const char* scr = getenv("OPENR_SPF_WHATIF_SCREEN");
-  if (has_ign && !(scr && atoi(scr) == 0) &&
+  if (has_ign && env_flag("OPENR_SPF_WHATIF_SCREEN", 1) &&
       (q->dist == DistPlan::SsspLds || q->dist == DistPlan::SsspGmem ||
        q->dist == DistPlan::Dstep)) {
     std::vector<uint32_t> base_srcs, base_of(nq);
@@ -11279,8 +10956,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
         if (!q->d_qctr && pool_malloc((void**)&q->d_qctr, 4) != hipSuccess) {
           return bail(fail(SPF_E_NOMEM, "what-if claim counter"));
         }
-        if (env_flag("OPENR_SPF_WHATIF_WORKLIST", 1) &&
-            pool_malloc((void**)&q->d_wl, ((size_t)nq + 2) * 4) != hipSuccess) {
+        if (pool_malloc((void**)&q->d_wl, ((size_t)nq + 2) * 4) != hipSuccess) {
           return bail(fail(SPF_E_NOMEM, "what-if work list"));
         }
         // queries whose failed link leaves the source: their own BFS launch
@@ -11537,12 +11213,10 @@ int launch_sssp(spf_query* q) {
     a.L = g->L;
     a.qctr = q->d_qctr;
     HIP_TRY(hipMemsetAsync(q->d_qctr, 0, 4, g->stream));
-    if (q->d_wl) {
-      SPF_LAUNCH(spf_whatif_worklist_kernel, dim3(1), dim3(1024), 0, g->stream, q->d_skip,
-                 q->nq, q->d_wl);
-      HIP_TRY(hipGetLastError());
-      a.wl = q->d_wl;
-    }
+    SPF_LAUNCH(spf_whatif_worklist_kernel, dim3(1), dim3(1024), 0, g->stream, q->d_skip, q->nq,
+               q->d_wl);
+    HIP_TRY(hipGetLastError());
+    a.wl = q->d_wl;
     if (env_flag("OPENR_SPF_WHATIF_STATS", 0)) {
       HIP_TRY(hipMalloc((void**)&a.stats, 8 * sizeof(unsigned long long)));
       HIP_TRY(hipMemsetAsync(a.stats, 0, 8 * sizeof(unsigned long long), g->stream));
@@ -11591,8 +11265,9 @@ int dispatch_flags(spf_query* q, bool unit, bool ign, bool gmem) {
               : launch_sssp<WMAX, false, false, false>(q);
 }
 
-template <int WMAX, bool IGN, uint32_t BS>
+template <int WMAX, bool IGN>
 int launch_dstep_t(spf_query* q) {
+  constexpr uint32_t BS = kDstepThreads;
   spf_graph* g = q->g;
   DstepArgs d;
   SsspArgs& a = d.s;
@@ -11616,21 +11291,13 @@ int launch_dstep_t(spf_query* q) {
   a.Vp = q->Vp;
   a.nbw = g->nbw;
   a.nq = q->nrows; // the batch + its helper sources (few-source rows plan)
-  a.G = g->G;
   a.ign_cap = q->dstep_ign_cap;
   a.skip = q->d_skip;
   // lanes per node: fewer than the median degree, so more nodes (and more
   // independent HBM gathers) are in flight per CU (4: measured on the 100k
   // WAN for the PULL pass of next-hop runs and for the push-only runs with
-  // 16-byte edge chunks); OPENR_SPF_DSTEP_G overrides
-  uint32_t G = 4;
-  if (const char* env = getenv("OPENR_SPF_DSTEP_G")) {
-    const int x = atoi(env);
-    if (x == 1 || x == 2 || x == 4 || x == 8 || x == 16 || x == 32 || x == 64) {
-      G = (uint32_t)x;
-    }
-  }
-  a.G = G;
+  // 16-byte edge chunks)
+  a.G = 4;
   d.shift = q->dstep_shift;
   d.fshift = q->dstep_fshift;
   d.noret = q->dstep_noret;
@@ -11662,8 +11329,7 @@ int launch_dstep_t(spf_query* q) {
   HIP_TRY(hipFuncSetAttribute(
       (const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
       (int)lds));
-  const char* st_env = getenv("OPENR_SPF_DSTEP_STATS");
-  if (st_env && atoi(st_env) == 1) {
+  if (env_dstep_stats()) {
     HIP_TRY(hipMalloc((void**)&d.stats, 8 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(d.stats, 0, 8 * sizeof(unsigned long long), g->stream));
   }
@@ -11682,18 +11348,19 @@ int launch_dstep_t(spf_query* q) {
   return SPF_OK;
 }
 
-template <uint32_t BS>
-int launch_dstep_bs(spf_query* q) {
+// 1024-thread workgroups: one per CU with the LDS bucket image (2 when the
+// buckets come from the distance row)
+int launch_dstep(spf_query* q) {
   const bool ign = q->has_ign;
   switch (q->wmax) {
   case 0:
-    return ign ? launch_dstep_t<0, true, BS>(q) : launch_dstep_t<0, false, BS>(q);
+    return ign ? launch_dstep_t<0, true>(q) : launch_dstep_t<0, false>(q);
   case 1:
-    return ign ? launch_dstep_t<1, true, BS>(q) : launch_dstep_t<1, false, BS>(q);
+    return ign ? launch_dstep_t<1, true>(q) : launch_dstep_t<1, false>(q);
   case 4:
-    return ign ? launch_dstep_t<4, true, BS>(q) : launch_dstep_t<4, false, BS>(q);
+    return ign ? launch_dstep_t<4, true>(q) : launch_dstep_t<4, false>(q);
   default:
-    return ign ? launch_dstep_t<16, true, BS>(q) : launch_dstep_t<16, false, BS>(q);
+    return ign ? launch_dstep_t<16, true>(q) : launch_dstep_t<16, false>(q);
   }
 }
 
@@ -11718,28 +11385,11 @@ int launch_dlds(spf_query* q) {
     return fail(SPF_E_INVALID, "internal: LDS-row plan without packed edges");
   }
   HIP_TRY(hipMemsetAsync(q->d_ovf, 0, 8, g->stream));
-  const char* st_env = getenv("OPENR_SPF_DSTEP_STATS");
-  if (st_env && atoi(st_env) == 1) {
+  if (env_dstep_stats()) {
     HIP_TRY(hipMalloc((void**)&a.stats, 8 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(a.stats, 0, 8 * sizeof(unsigned long long), g->stream));
   }
-  // lanes per node (OPENR_SPF_DSTEP_LG 1/2/4/8) and the two-node prefetch
-  // (OPENR_SPF_DSTEP_LPF=0 disables)
-  const bool pf = env_flag("OPENR_SPF_DSTEP_LPF", 1);
-  auto kern = pf ? spf_dlds_kernel<1024, 4, true> : spf_dlds_kernel<1024, 4, false>;
-  switch (env_u32("OPENR_SPF_DSTEP_LG", 4)) {
-  case 1:
-    kern = pf ? spf_dlds_kernel<1024, 1, true> : spf_dlds_kernel<1024, 1, false>;
-    break;
-  case 2:
-    kern = pf ? spf_dlds_kernel<1024, 2, true> : spf_dlds_kernel<1024, 2, false>;
-    break;
-  case 8:
-    kern = pf ? spf_dlds_kernel<1024, 8, true> : spf_dlds_kernel<1024, 8, false>;
-    break;
-  default:
-    break;
-  }
+  auto kern = spf_dlds_kernel<1024>;
   HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)q->dlds_lds));
   SPF_LAUNCH_AS("spf_dlds_kernel", kern, dim3(q->dlds_grid), dim3(1024), q->dlds_lds, g->stream, a);
@@ -11757,12 +11407,6 @@ int launch_dlds(spf_query* q) {
             q->nq, h[0], h[1], h[4], h[5], h[6], h[7], novf);
   }
   return SPF_OK;
-}
-
-// 1024-thread workgroups: one per CU with the LDS bucket image (2 when the
-// buckets come from the distance row)
-int launch_dstep(spf_query* q) {
-  return q->dstep_bs == 512 ? launch_dstep_bs<512>(q) : launch_dstep_bs<1024>(q);
 }
 
 int launch_msdstep(spf_query* q) {
@@ -11858,11 +11502,10 @@ int launch_nh_rows(spf_query* q, bool unit) {
 // writes them as 16-byte runs: fabric msbfs 0.228 -> 0.155 ms, next hops
 // 0.451 -> 0.499 ms, step 0.691 -> 0.666 ms (profiles/r03w)
 inline bool lvl_only(const spf_query* q) {
-  // (the byte pass chosen when the query was created, q->nl_swar -- not the
-  // environment at run time, which could pair the BFS's skipped distance
-  // stores with a next-hop kernel that does not write them)
-  return q->nh == NhPlan::Levels && !q->zvars && q->nl_swar &&
-         env_flag("OPENR_MS_LVL_ONLY", 1);
+  // (both as latched when the query was created -- not the environment at
+  // run time, which could pair the BFS's skipped distance stores with a
+  // next-hop launch that does not write them)
+  return q->nh == NhPlan::Levels && !q->zvars && q->nl_swar && q->ms_lvl_only;
 }
 
 int launch_msbfs(spf_query* q, bool unit) {
@@ -11888,7 +11531,6 @@ int launch_msbfs(spf_query* q, bool unit) {
   a.zlist = nullptr;
   a.nz = 0;
   a.lvl_only = lvl_only(q) ? 1u : 0u;
-  a.norec = env_u32("OPENR_MS_NOREC", 0);
   a.blocked = q->d_ms_blocked;
   q->ms_par ^= 1u;
   a.flags = q->d_flags + q->ms_par;
@@ -11909,8 +11551,9 @@ int launch_msbfs(spf_query* q, bool unit) {
   }
   const uint32_t K = (g->V + kMsThreads - 1) / kMsThreads;
   const void* kern = nullptr;
-  // OPENR_MS_GEN=1: the general instance for every batch (A/B of the plain one)
-  const bool gen = q->ms_ign || a.wrec || q->zvars || env_flag("OPENR_MS_GEN", 0);
+  // the general instance (ignore masks, wave-recorded levels and zero-metric
+  // closure compiled in) only for the batches that need one of them
+  const bool gen = q->ms_ign || a.wrec || q->zvars;
 #define MS_PICK(MT, KM)                                                                      \
   kern = gen ? (sell ? (const void*)spf_msbfs_kernel<MT, KM, true, true>                     \
                      : (const void*)spf_msbfs_kernel<MT, KM, false, true>)                   \
@@ -11921,7 +11564,7 @@ int launch_msbfs(spf_query* q, bool unit) {
       MS_PICK(uint64_t, 4);
     } else if (K <= 8) {
       MS_PICK(uint64_t, 8);
-    } else if (K <= 10 && env_flag("OPENR_MS_K10", 1)) {
+    } else if (K <= 10) {
       // the 10k fabric (K = 10): the plain instance spills 2 VGPRs, not 24
       MS_PICK(uint64_t, 10);
     } else if (K <= 12) {
@@ -12052,7 +11695,6 @@ int launch_nh_levels(spf_query* q, bool unit) {
   a.lvl = q->d_lvl;
   a.dist = (const uint32_t*)q->d_dist;
   a.flags = q->d_flags ? q->d_flags + q->ms_par : nullptr;
-  a.nt_store = env_flag("OPENR_NL_NT", 0) ? 1u : 0u;
   a.nh_off = q->d_nh_off;
   a.nh_w = q->d_nh_w;
   a.nh_out = q->d_nh;
@@ -12064,8 +11706,6 @@ int launch_nh_levels(spf_query* q, bool unit) {
   a.Vp8 = q->Vp8;
   a.nq = q->nq;
   a.scale = unit ? 1u : (q->zvars ? q->zscale : g->uniform);
-  a.xcd_swizzle = env_flag("OPENR_NL_XCD", 0);
-  a.held_words = env_flag("OPENR_NL_HELD", 1);
   a.zvar = q->d_zvar;
   a.lvl_vstride = (uint64_t)q->nrows * q->Vp8;
   a.dist_vstride = (uint64_t)q->nrows * q->Vp;
@@ -12079,24 +11719,13 @@ int launch_nh_levels(spf_query* q, bool unit) {
   if (q->nl_swar) {
     // held kernel: every source with <= kNsHeldMax mask words; the generic
     // byte kernel: the rest (q->d_big), or every source after a deep BFS
-    // threads per block (OPENR_NL_HT = 256 / 512 / 1024; chunk = 4 nodes per thread)
-    const uint32_t ht = env_u32("OPENR_NL_HT", 256);
-    const uint32_t T = ht == 1024 ? 1024u : (ht == 512 ? 512u : 256u);
-    uint64_t hblocks = (uint64_t)q->nq * ((g->V + 4 * T - 1) / (4 * T));
-    if (q->d_held_order && q->held_t == T) {
-      a.held_order = q->d_held_order;
-      a.held_nch = q->held_nch;
-      hblocks = q->held_blocks;
-    }
+    const uint64_t hblocks = (uint64_t)q->nq * ((g->V + 1023) / 1024);
     if (hblocks > 0x7FFFFFFFull) {
       return fail(SPF_E_UNSUPPORTED, "batch too large for the next-hop pass");
     }
-    const uint32_t* nolist = nullptr;
-    if (q->has_v2 && q->v2_gen == g->nbr_gen && T == 256 && !a.held_order) {
+    if (q->has_v2 && q->v2_gen == g->nbr_gen) {
       // v2: solo items and shared-neighbour groups (spf_nh_levels_v2_kernel)
-      const uint64_t vblocks = q->v2.order == 5 ? (uint64_t)q->v2.nmap
-                                                : (uint64_t)(q->v2.nsolo + q->v2.nsub) *
-                                                      ((g->V + 1023) / 1024);
+      const uint64_t vblocks = (uint64_t)(q->v2.nsolo + q->v2.nsub) * ((g->V + 1023) / 1024);
       if (vblocks && q->v2.trit) {
         SPF_LAUNCH((spf_nh_levels_v2_kernel<256, true>), dim3((uint32_t)vblocks), dim3(256), 0,
                            g->stream, a, q->v2);
@@ -12104,29 +11733,24 @@ int launch_nh_levels(spf_query* q, bool unit) {
         SPF_LAUNCH((spf_nh_levels_v2_kernel<256, false>), dim3((uint32_t)vblocks), dim3(256), 0,
                            g->stream, a, q->v2);
       }
-    } else if (T == 1024) {
-      SPF_LAUNCH((spf_nh_levels_held_kernel<1024, kNsHeldMax>), dim3((uint32_t)hblocks),
-                         dim3(1024), 0, g->stream, a, nolist, 0u);
-    } else if (T == 512) {
-      SPF_LAUNCH((spf_nh_levels_held_kernel<512, kNsHeldMax>), dim3((uint32_t)hblocks),
-                         dim3(512), 0, g->stream, a, nolist, 0u);
     } else {
+      const uint32_t* nolist = nullptr;
       SPF_LAUNCH((spf_nh_levels_held_kernel<256, kNsHeldMax>), dim3((uint32_t)hblocks),
                          dim3(256), 0, g->stream, a, nolist, 0u);
     }
     HIP_TRY(hipGetLastError());
-    if (q->nmid && env_flag("OPENR_NL_WIDE", 1)) {
+    if (q->nmid) {
       // sources with 4-8 words: the same per-(source, chunk) pass
       const uint64_t mblocks = (uint64_t)q->nmid * ((g->V + 1023) / 1024);
       SPF_LAUNCH((spf_nh_levels_held_kernel<256, kNsHeldWide>), dim3((uint32_t)mblocks),
                          dim3(256), 0, g->stream, a, (const uint32_t*)q->d_big, q->nmid);
       HIP_TRY(hipGetLastError());
     }
-    const uint32_t skip = env_flag("OPENR_NL_WIDE", 1) ? q->nmid : 0;
+    const uint32_t skip = q->nmid;
     // with no wide source left the kernel only serves a BFS deeper than 254
     // levels, which a graph of at most 254 nodes cannot have: no launch (a
     // small area's RouteDb batch, e.g. the 10x10 grid)
-    if (q->nbig == skip && g->V <= 254 && env_flag("OPENR_NL_SWAR_SKIP", 1)) {
+    if (q->nbig == skip && g->V <= 254) {
       return SPF_OK;
     }
     const uint32_t grid = std::max<uint32_t>(q->nbig - skip, std::min<uint32_t>(q->nq, 1024));
@@ -12205,9 +11829,6 @@ int launch_wide(spf_query* q) {
   a.unit = (q->flags & SPF_F_UNIT_METRIC) ? 1 : 0;
   a.n_zero = a.unit ? 0 : g->n_zero;
   a.delta = a.unit ? 1 : g->wide_delta;
-  if (const char* dv = getenv("OPENR_SPF_WIDE_DELTA")) {
-    a.delta = std::max<uint64_t>(1, strtoull(dv, nullptr, 10));
-  }
   a.want_nh = (q->flags & SPF_F_NEXTHOPS) ? 1 : 0;
   if (g->nbw * 32 < g->V) {
     return fail(SPF_E_INVALID, "bitmap words do not cover the nodes");
@@ -12347,9 +11968,8 @@ int run_screen(spf_query* q) {
   a.mark_heavy = q->repair ? 1u : 0u;
   a.wh_mark = q->repair ? q->d_wh_mark : nullptr;
   // screened rows straight into the output layout (the narrowing pass skips
-  // them: OPENR_SPF_SCREEN_DIRECT=0 keeps the word copy)
-  q->screen_direct = q->narrow && !q->nh_direct && a.want_nh && q->d_nhb && q->d_nhb_off &&
-                     env_flag("OPENR_SPF_SCREEN_DIRECT", 1);
+  // them)
+  q->screen_direct = q->narrow && !q->nh_direct && a.want_nh && q->d_nhb && q->d_nhb_off;
   if (q->screen_direct) {
     a.nhb = q->d_nhb;
     a.nhb_off = q->d_nhb_off;
@@ -12444,14 +12064,11 @@ int run_screen(spf_query* q) {
     // on its own (high-priority) stream beside the SSSP of the rest, the
     // graph stream joining it after that launch (launch_sssp): fabric batch
     // 1.38 ms, against 1.54 ms in order on the graph stream
-    // (OPENR_SPF_WHATIF_HEAVY_STREAM=0; the kernel alone is 0.75 ms there,
-    // beside the SSSP its two 122 KB workgroups wait for free CUs)
-    const bool side = env_flag("OPENR_SPF_WHATIF_HEAVY_STREAM", 1);
-    hipStream_t hstream = side ? q->wh_stream : g->stream;
-    if (side) {
-      HIP_TRY(hipEventRecord(q->wh_ev0, g->stream));
-      HIP_TRY(hipStreamWaitEvent(q->wh_stream, q->wh_ev0, 0));
-    }
+    // (the kernel alone is 0.75 ms there, beside the SSSP its two 122 KB
+    // workgroups wait for free CUs)
+    hipStream_t hstream = q->wh_stream;
+    HIP_TRY(hipEventRecord(q->wh_ev0, g->stream));
+    HIP_TRY(hipStreamWaitEvent(q->wh_stream, q->wh_ev0, 0));
     if (q->wh_pull) {
       SPF_LAUNCH(spf_whatif_pull_kernel, dim3((uint32_t)q->wh_pull_cand.size()),
                  dim3(kWhThreads), lds, hstream, h);
@@ -12460,13 +12077,11 @@ int run_screen(spf_query* q) {
                  dim3(kWhThreads), lds, hstream, h);
     }
     HIP_TRY(hipGetLastError());
-    if (side) {
-      HIP_TRY(hipEventRecord(q->wh_ev1, q->wh_stream));
-      q->wh_pending = true;
-    }
+    HIP_TRY(hipEventRecord(q->wh_ev1, q->wh_stream));
+    q->wh_pending = true;
     if (h.stats) {
       std::vector<unsigned long long> hs(6 * q->wh_pull_cand.size());
-      HIP_TRY(hipStreamSynchronize(side ? q->wh_stream : g->stream));
+      HIP_TRY(hipStreamSynchronize(q->wh_stream));
       HIP_TRY(hipMemcpy(hs.data(), h.stats, hs.size() * 8, hipMemcpyDeviceToHost));
       HIP_TRY(hipFree(h.stats));
       for (size_t i = 0; i < q->wh_pull_cand.size(); ++i) {
@@ -13226,8 +12841,7 @@ int spf_query_trace_paths(
     // a state's tag is its query index + 1)
     // 16 waves per CU (a wave's DFS is a chain of L2 round trips: the more
     // queries in flight, the better); scratch bounded for large graphs
-    const uint32_t wpc = std::max<uint32_t>(1, std::min<uint32_t>(16, env_u32("OPENR_SPF_TRACE_WPC", 16)));
-    const uint32_t maxw = g->V > 50000 ? 1024u : (uint32_t)g->num_cus * wpc;
+    const uint32_t maxw = g->V > 50000 ? 1024u : (uint32_t)g->num_cus * 16;
     const uint32_t nw = std::min<uint32_t>((count + kTcWaves - 1) / kTcWaves * kTcWaves, maxw);
     const uint32_t acap = std::max<uint32_t>(1024, std::min<uint32_t>(g->E, 1u << 15));
     // node states | arenas | the query-claim counter
@@ -13253,7 +12867,7 @@ int spf_query_trace_paths(
     // device's (KSP2 build 58 -> 74 ms, profiles/r05s)
     ta.budget = env_u32("OPENR_SPF_TRACE_BUDGET", heavy ? kTcHeavyBudget : 0xFFFFFFFFu);
     HIP_TRY(hipMemsetAsync(q->d_tcs, 0, (size_t)nw * g->V * sizeof(uint4), g->stream));
-    if (env_flag("OPENR_SPF_TRACE_DYN", 1) && count > nw) {
+    if (count > nw) {
       ta.qctr = reinterpret_cast<uint32_t*>(q->d_tcs + o_ctr);
       HIP_TRY(hipMemsetAsync(ta.qctr, 0, 4, g->stream));
     }
@@ -13371,9 +12985,8 @@ int spf_query_trace_paths(
       if (stats) {
         HIP_TRY(hipMalloc((void**)&h.hstat, (size_t)nh * 32));
       }
-      h.xcd = env_flag("OPENR_SPF_TRACE_HEAVY_XCD", 1) ? 1u : 0u;
       const uint64_t bq = hv_blocks(hv_nsmall, g->V - hv_nsmall);
-      const uint64_t nblk = h.xcd ? 8 * ((nh + 7) / 8) * bq : (uint64_t)nh * bq;
+      const uint64_t nblk = 8 * ((nh + 7) / 8) * bq; // 8 queries' blocks interleaved, one per XCD
       SPF_LAUNCH(spf_trace_heavy_build_kernel, dim3((uint32_t)nblk), dim3(64 * kHvWaves), 0,
                  g->stream, h);
       h.L = g->L;

@@ -555,7 +555,10 @@ def test_nh_levels_swar_matches_scalar(gpu_ready, case, monkeypatch):
     (spf_nh_levels_kernel) on the same MS-BFS rows, and both against the
     literal replay on a few sources: drained neighbours (next hop only to
     themselves), sources with 1-3, 4-8 and more mask words, a ragged last
-    chunk, and a BFS deeper than 254 levels (the 32-bit-row branch)."""
+    chunk, and a BFS deeper than 254 levels (the 32-bit-row branch).  The
+    default run takes the v2 kernel for the sources with at most 3 words; a
+    third run (OPENR_NL_V2=0) takes the held kernel's main instance for them
+    and must return the same masks and distances bit for bit."""
     rng = random.Random({"random": 5, "hubs": 6, "wide_hubs": 8, "deep": 7}[case])
     if case == "deep":
         V = 700  # a 600-node chain hanging off a random core: levels > 255
@@ -589,6 +592,18 @@ def test_nh_levels_swar_matches_scalar(gpu_ready, case, monkeypatch):
     if not (ma == mb).all():
         bad = int(np.flatnonzero(ma != mb)[0])
         pytest.fail(f"mask word {bad} differs: {ma[bad]:#x} vs {mb[bad]:#x}")
+    assert "spf_nh_levels_v2_kernel" in a.kernels()
+    monkeypatch.setenv("OPENR_NL_SWAR", "1")
+    monkeypatch.setenv("OPENR_NL_V2", "0")
+    h = g.query(srcs, flags).run()
+    assert "spf_nh_levels_held_kernel" in h.kernels()
+    assert "spf_nh_levels_v2_kernel" not in h.kernels()
+    mh = h.fetch_nexthops(0, V)
+    if not (ma == mh).all():
+        bad = int(np.flatnonzero(ma != mh)[0])
+        pytest.fail(f"held kernel: mask word {bad} differs: {ma[bad]:#x} vs {mh[bad]:#x}")
+    for i in range(V):
+        assert (a.dist(i) == h.dist(i)).all(), i
     probe = [0, 7, 8, 9, V - 1, V // 2] if case != "deep" else [0, 99, 650, 699]
     check_query(csr, a, [int(s) for s in srcs], False, rows=set(probe))
 
