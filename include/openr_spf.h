@@ -452,6 +452,48 @@ int spf_route_table_diff(spf_route_table* older, spf_route_table* newer, uint32_
 /* Changed-prefix bitmap of row i from the last diff: bits[ceil(P/64)]. */
 int spf_route_table_changed(spf_route_table* t, uint32_t i, uint64_t* bits);
 
+/* The maps of spf_route_table_diff_mapped (host arrays, read during the
+ * call).  A null array is the identity map (a null dirty_off: no dirty
+ * announcers); SPF_MAP_NONE marks an entry with no counterpart. */
+#define SPF_MAP_NONE 0xFFFFFFFFu
+typedef struct spf_route_diff_map {
+  const uint32_t* row_of;    /* [newer rows]: older row, or NONE */
+  const uint32_t* col_of;    /* [newer P]: older column, or NONE; injective */
+  const uint32_t* gone_cols; /* [num_gone]: older columns with no newer counterpart */
+  const uint32_t* node_of;   /* [older V]: newer node id, or NONE */
+  const uint32_t* link_off;  /* [newer rows + 1]: offsets into link_of */
+  const uint32_t* link_of;   /* per newer row, per up link in CSR order: the older row's bit
+                                position, or NONE; injective within a row.  A row's segment is
+                                its link count long, or empty: identity for that row */
+  const uint32_t* dirty_off; /* [newer P + 1]: offsets into dirty_ann */
+  const uint32_t* dirty_ann; /* newer node ids: announcers of the column whose prefix entry
+                                changed (a route whose best is one of them is an update) */
+  uint32_t num_gone;
+} spf_route_diff_map;
+/* The route delta of every node (getRouteDelta, Decision.cpp:47-85) between
+ * tables whose nodes, columns and link layouts differ (a link down or up, a
+ * node joining or leaving, a prefix announced or withdrawn): cell (i, p) of
+ * `newer` is compared with cell (row_of[i], col_of[p]) of `older`, link masks
+ * through link_of as sets of links, best announcers through node_of.  Changed
+ * iff exactly one side has a route (metric != UINT32_MAX; a cell without a
+ * counterpart has none), or both have one and the metric, the mapped best,
+ * the link set or (SPF_RT_LFA) a link's own metric differs, or the newer best
+ * is a dirty announcer of the column.  For every gone column the older cell's
+ * route is a delete (spf_route_table_changed_gone).  changed[i] = changed
+ * newer columns + deleted gone columns of row i; the bitmaps are kept in
+ * `newer`.  Rows whose links keep their positions compare mask words like
+ * spf_route_table_diff; a remapped row may have at most 1024 links.
+ * SPF_E_INVALID for an out-of-range entry or a col_of / link_of that is not
+ * injective, SPF_E_UNSUPPORTED when the tables differ in SPF_RT_LFA or in
+ * device.  A null `map` is all identity. */
+int spf_route_table_diff_mapped(
+    spf_route_table* older, spf_route_table* newer, const spf_route_diff_map* map,
+    uint32_t* changed);
+/* Deleted-column bitmap of row i from the last spf_route_table_diff_mapped
+ * (the deletes of getRouteDelta, Decision.cpp:47-85): bit g set iff the older
+ * row had a route in gone_cols[g]; bits[ceil(num_gone/64)]. */
+int spf_route_table_changed_gone(spf_route_table* t, uint32_t i, uint64_t* bits);
+
 /* ---- multi-GPU all-sources tables ----
  * The reference computes every SpfResult on the one Decision thread
  * (getSpfResult, LinkState.cpp:791-801; all sources = Decision::

@@ -91,6 +91,8 @@ EXPORTED_SYMBOLS = (
     "spf_route_table_fetch",
     "spf_route_table_diff",
     "spf_route_table_changed",
+    "spf_route_table_diff_mapped",
+    "spf_route_table_changed_gone",
     "spf_cluster_unique_id",
     "spf_cluster_create_local",
     "spf_cluster_create_rank",
@@ -138,6 +140,8 @@ SPF_DELTA_ADDED = 2
 SPF_SCOPE_ALL = 0
 SPF_SCOPE_TAIL_ONLY = 1
 SPF_SCOPE_NOT_TAIL = 2
+SPF_RT_LFA = 0x1
+SPF_MAP_NONE = 0xFFFFFFFF
 
 # numpy twin of spf_edge_delta (same layout: 24 bytes)
 EDGE_DELTA_DTYPE = np.dtype(
@@ -224,6 +228,31 @@ def _query_desc(src, flags, ignore=None):
         flags,
     )
     return d, keep
+
+
+class _RouteDiffMap(C.Structure):
+    _fields_ = [
+        ("row_of", C.POINTER(C.c_uint32)),
+        ("col_of", C.POINTER(C.c_uint32)),
+        ("gone_cols", C.POINTER(C.c_uint32)),
+        ("node_of", C.POINTER(C.c_uint32)),
+        ("link_off", C.POINTER(C.c_uint32)),
+        ("link_of", C.POINTER(C.c_uint32)),
+        ("dirty_off", C.POINTER(C.c_uint32)),
+        ("dirty_ann", C.POINTER(C.c_uint32)),
+        ("num_gone", C.c_uint32),
+    ]
+
+
+def _route_diff_map(row_of=None, col_of=None, gone_cols=None, node_of=None, link_off=None,
+                    link_of=None, dirty_off=None, dirty_ann=None):
+    """(spf_route_diff_map, arrays it points into); None stays a null array
+    (identity / no dirty announcers)."""
+    keep = [None if x is None else np.ascontiguousarray(x, dtype=np.uint32)
+            for x in (row_of, col_of, gone_cols, node_of, link_off, link_of, dirty_off, dirty_ann)]
+    ptr = [None if x is None or len(x) == 0 else _p(x, C.c_uint32) for x in keep]
+    m = _RouteDiffMap(*ptr, 0 if keep[2] is None else len(keep[2]))
+    return m, keep
 
 
 _lib = None
@@ -346,6 +375,18 @@ def load():
         "spf_table_fetch_levels": (C.c_int, [vp, u32, u32, C.POINTER(C.c_uint8)]),
         "spf_table_row_form": (C.c_int, [vp, pu32, pu32, pu64]),
         "spf_table_levels_buffer": (C.c_int, [vp, u32, C.POINTER(vp), pu64, pu64]),
+        "spf_route_table_create": (C.c_int, [vp, u32, pu32, pu32, C.POINTER(vp)]),
+        "spf_route_table_create_ex": (C.c_int, [vp, u32, pu32, pu32, u32, C.POINTER(vp)]),
+        "spf_route_table_destroy": (C.c_int, [vp]),
+        "spf_route_table_run": (C.c_int, [vp]),
+        "spf_route_table_elapsed_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "spf_route_table_link_words": (C.c_int, [vp, u32]),
+        "spf_route_table_fetch": (C.c_int, [vp, u32, pu32, pu32, pu64]),
+        "spf_route_table_fetch_link_metrics": (C.c_int, [vp, u32, pu32]),
+        "spf_route_table_diff": (C.c_int, [vp, vp, pu32]),
+        "spf_route_table_changed": (C.c_int, [vp, u32, pu64]),
+        "spf_route_table_diff_mapped": (C.c_int, [vp, vp, C.POINTER(_RouteDiffMap), pu32]),
+        "spf_route_table_changed_gone": (C.c_int, [vp, u32, pu64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
@@ -863,6 +904,95 @@ class Query:
             "device_rows",
         )
         return dp.value, eb.value, np_.value, nt.value
+
+
+class RouteTable:
+    """All-nodes route table over a run Query (spf_route_table_*): prefix p
+    is announced by announcers[p] (node ids)."""
+
+    def __init__(self, query: Query, announcers, flags=0):
+        lib = load()
+        self.query = query
+        self.P = len(announcers)
+        off = np.zeros(self.P + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(a) for a in announcers])
+        flat = [int(x) for a in announcers for x in a]
+        ann = np.asarray(flat if flat else [0], dtype=np.uint32)
+        h = C.c_void_p()
+        _check(lib.spf_route_table_create_ex(query.h, self.P, _p(off, C.c_uint32),
+                                             _p(ann, C.c_uint32), flags, C.byref(h)),
+               "spf_route_table_create_ex")
+        self.h = h
+        self.n = query.n
+        self.lfa = bool(flags & SPF_RT_LFA)
+        self.num_gone = 0
+
+    def close(self):
+        if self.h:
+            load().spf_route_table_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self):
+        _check(load().spf_route_table_run(self.h), "spf_route_table_run")
+        return self
+
+    def link_words(self, i: int) -> int:
+        return load().spf_route_table_link_words(self.h, i)
+
+    def fetch(self, i: int):
+        """Row i: (metric [P], best [P], links [P, link_words(i)])."""
+        W = self.link_words(i)
+        metric = np.zeros(max(self.P, 1), dtype=np.uint32)
+        best = np.zeros(max(self.P, 1), dtype=np.uint32)
+        links = np.zeros(max(self.P * W, 1), dtype=np.uint64)
+        _check(load().spf_route_table_fetch(self.h, i, _p(metric, C.c_uint32), _p(best, C.c_uint32),
+                                            _p(links, C.c_uint64)), "spf_route_table_fetch")
+        return metric[: self.P], best[: self.P], links[: self.P * W].reshape(self.P, W)
+
+    def fetch_link_metrics(self, i: int, deg: int) -> np.ndarray:
+        """SPF_RT_LFA: per-link metrics of row i, [P, deg]."""
+        out = np.zeros(max(self.P * deg, 1), dtype=np.uint32)
+        _check(load().spf_route_table_fetch_link_metrics(self.h, i, _p(out, C.c_uint32)),
+               "spf_route_table_fetch_link_metrics")
+        return out[: self.P * deg].reshape(self.P, deg)
+
+    def diff(self, older: "RouteTable") -> np.ndarray:
+        """spf_route_table_diff: changed columns per row (equal layouts)."""
+        out = np.zeros(max(self.n, 1), dtype=np.uint32)
+        _check(load().spf_route_table_diff(older.h, self.h, _p(out, C.c_uint32)),
+               "spf_route_table_diff")
+        return out[: self.n]
+
+    def diff_mapped(self, older: "RouteTable", **maps) -> np.ndarray:
+        """spf_route_table_diff_mapped: changed + deleted columns per row;
+        `maps` are the arrays of spf_route_diff_map (absent: identity)."""
+        m, keep = _route_diff_map(**maps)
+        out = np.zeros(max(self.n, 1), dtype=np.uint32)
+        _check(load().spf_route_table_diff_mapped(older.h, self.h, C.byref(m), _p(out, C.c_uint32)),
+               "spf_route_table_diff_mapped")
+        self.num_gone = int(m.num_gone)
+        del keep
+        return out[: self.n]
+
+    def changed(self, i: int) -> np.ndarray:
+        """Changed-column bitmap of row i from the last diff, as bools [P]."""
+        bits = np.zeros(max((self.P + 63) // 64, 1), dtype=np.uint64)
+        _check(load().spf_route_table_changed(self.h, i, _p(bits, C.c_uint64)),
+               "spf_route_table_changed")
+        return np.unpackbits(bits.view(np.uint8), bitorder="little")[: self.P].astype(bool)
+
+    def changed_gone(self, i: int) -> np.ndarray:
+        """Deleted gone-column bitmap of row i from the last mapped diff."""
+        bits = np.zeros(max((self.num_gone + 63) // 64, 1), dtype=np.uint64)
+        _check(load().spf_route_table_changed_gone(self.h, i, _p(bits, C.c_uint64)),
+               "spf_route_table_changed_gone")
+        return np.unpackbits(bits.view(np.uint8), bitorder="little")[: self.num_gone].astype(bool)
 
 
 # ------------------------------------------------- multi-GPU tables (RCCL)

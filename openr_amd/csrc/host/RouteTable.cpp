@@ -298,6 +298,7 @@ AllNodesRouteTable::AllNodesRouteTable(
       // name ranks) -- the order of a label -> sorted names map, without one
       std::vector<std::pair<int32_t, uint32_t>> lab;
       lab.reserve(names_.size());
+      nodeLabel_.assign(names_.size(), 0);
       for (const auto& [node, db] : ls.getAdjacencyDatabases()) {
         if (db.nodeLabel == 0 || !isMplsLabelValid(db.nodeLabel)) {
           continue;
@@ -305,6 +306,7 @@ AllNodesRouteTable::AllNodesRouteTable(
         auto it = ids_.find(node);
         if (it != ids_.end()) {
           lab.emplace_back(db.nodeLabel, it->second);
+          nodeLabel_[it->second] = db.nodeLabel;
         }
       }
       std::sort(lab.begin(), lab.end());
@@ -560,20 +562,191 @@ std::vector<uint32_t> AllNodesRouteTable::diff(const AllNodesRouteTable& older) 
     throw std::invalid_argument(
         "AllNodesRouteTable::diff: tables with BGP columns (AllAreasRouteTable) are not diffed");
   }
+  if (older.lfa_ != lfa_ || older.area_ != area_) {
+    throw std::invalid_argument("AllNodesRouteTable::diff: different areas or LFA modes");
+  }
   if (older.names_ != names_ || older.prefixes_ != prefixes_ || older.row_ != row_ ||
-      !sameOwners || older.lfa_ != lfa_) {
-    throw std::invalid_argument(
-        "AllNodesRouteTable::diff: different nodes, prefixes, node labels or links");
+      !sameOwners) {
+    return diffMapped(older);
+  }
+  // a changed PrefixEntry of a kept announcer changes routes whose cells are
+  // equal: only the mapped diff (dirty announcers) sees it
+  for (size_t p = 0; p < prefixes_.size(); ++p) {
+    for (const auto& a : announcers_[p]) {
+      for (const auto& o : older.announcers_[p]) {
+        if (o.id == a.id && !(o.entry == a.entry)) {
+          return diffMapped(older);
+        }
+      }
+    }
   }
   std::vector<uint32_t> changed(names_.size());
+  const auto tp = std::chrono::steady_clock::now();
   if (int s = spf_route_table_diff(older.table_, table_, changed.data()); s != SPF_OK) {
+    if (s == SPF_E_UNSUPPORTED) {
+      // same row offsets, other neighbours behind them (a link moved)
+      return diffMapped(older);
+    }
+    tableFailure("spf_route_table_diff", s);
+  }
+  diffCallMs_ = (float)usSince(tp) / 1000.f;
+  diffed_ = true;
+  mapped_ = false;
+  goneCols_.clear();
+  rowOf_.resize(names_.size());
+  for (uint32_t i = 0; i < rowOf_.size(); ++i) {
+    rowOf_[i] = i;
+  }
+  older_ = &older;
+  return changed;
+}
+
+std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& older) {
+  const uint32_t V = (uint32_t)names_.size(), Va = (uint32_t)older.names_.size();
+  const size_t P = prefixes_.size(), C = P + owners_.size();
+  const size_t Pa = older.prefixes_.size(), Ca = Pa + older.owners_.size();
+  // rows and best announcers: by node name
+  std::vector<uint32_t> rowOf(V, SPF_MAP_NONE), nodeOf(Va, SPF_MAP_NONE);
+  for (uint32_t i = 0; i < V; ++i) {
+    auto it = older.ids_.find(names_[i]);
+    if (it != older.ids_.end()) {
+      rowOf[i] = it->second;
+      nodeOf[it->second] = i;
+    }
+  }
+  // columns: unicast by prefix, node labels by (label, owner name)
+  std::vector<uint32_t> colOf(C, SPF_MAP_NONE), gone;
+  std::vector<uint8_t> kept(Ca, 0);
+  {
+    std::unordered_map<thrift::IpPrefix, uint32_t> colA;
+    colA.reserve(Pa);
+    for (uint32_t p = 0; p < Pa; ++p) {
+      colA.emplace(older.prefixes_[p], p);
+    }
+    for (size_t p = 0; p < P; ++p) {
+      auto it = colA.find(prefixes_[p]);
+      if (it != colA.end()) {
+        colOf[p] = it->second;
+        kept[it->second] = 1;
+      }
+    }
+    std::map<std::pair<int32_t, uint32_t>, uint32_t> labA; // (label, newer owner id) -> column
+    for (size_t k = 0; k < older.owners_.size(); ++k) {
+      const uint32_t id = nodeOf[older.owners_[k].id];
+      if (id != SPF_MAP_NONE) {
+        labA.emplace(std::make_pair(older.owners_[k].label, id), (uint32_t)(Pa + k));
+      }
+    }
+    for (size_t k = 0; k < owners_.size(); ++k) {
+      auto it = labA.find({owners_[k].label, owners_[k].id});
+      if (it != labA.end()) {
+        colOf[P + k] = it->second;
+        kept[it->second] = 1;
+      }
+    }
+    for (uint32_t c = 0; c < Ca; ++c) {
+      if (!kept[c]) {
+        gone.push_back(c);
+      }
+    }
+  }
+  // links: by Link identity (node and interface names); a link whose
+  // next-hop addresses, interface or area differ from this node has no
+  // counterpart.  Rows whose links all keep their positions get an empty
+  // segment (identity).
+  std::vector<uint32_t> linkOff(V + 1, 0), linkOf;
+  {
+    auto same = [](const Link& a, const Link& b, const std::string& node) {
+      return a == b && a.getArea() == b.getArea() &&
+          a.getIfaceFromNode(node) == b.getIfaceFromNode(node) &&
+          a.getNhV4FromNode(node) == b.getNhV4FromNode(node) &&
+          a.getNhV6FromNode(node) == b.getNhV6FromNode(node);
+    };
+    std::unordered_multimap<size_t, uint32_t> byHash;
+    for (uint32_t i = 0; i < V; ++i) {
+      linkOff[i + 1] = linkOff[i];
+      const uint32_t ia = rowOf[i];
+      if (ia == SPF_MAP_NONE) {
+        continue;
+      }
+      const uint32_t e0 = row_[i], deg = row_[i + 1] - e0;
+      const uint32_t a0 = older.row_[ia], dega = older.row_[ia + 1] - a0;
+      bool ident = deg == dega;
+      for (uint32_t j = 0; ident && j < deg; ++j) {
+        ident = same(*halfLink_[e0 + j], *older.halfLink_[a0 + j], names_[i]);
+      }
+      if (ident) {
+        continue;
+      }
+      byHash.clear();
+      for (uint32_t j = 0; j < dega; ++j) {
+        byHash.emplace(older.halfLink_[a0 + j]->hash, j);
+      }
+      for (uint32_t j = 0; j < deg; ++j) {
+        uint32_t t = SPF_MAP_NONE;
+        const Link& l = *halfLink_[e0 + j];
+        auto [lo, hi] = byHash.equal_range(l.hash);
+        for (auto it = lo; it != hi; ++it) {
+          if (same(l, *older.halfLink_[a0 + it->second], names_[i])) {
+            t = it->second;
+            byHash.erase(it); // (a link is one bit of the row: injective)
+            break;
+          }
+        }
+        linkOf.push_back(t);
+      }
+      linkOff[i + 1] = (uint32_t)linkOf.size();
+    }
+  }
+  // dirty announcers: same node, PrefixEntry unequal
+  std::vector<uint32_t> dirtyOff(C + 1, 0), dirtyAnn;
+  for (size_t p = 0; p < C; ++p) {
+    if (p < P && colOf[p] != SPF_MAP_NONE) {
+      const auto& olds = older.announcers_[colOf[p]];
+      for (const auto& a : announcers_[p]) {
+        for (const auto& o : olds) {
+          if (nodeOf[o.id] == a.id && !(o.entry == a.entry)) {
+            dirtyAnn.push_back(a.id);
+          }
+        }
+      }
+    }
+    dirtyOff[p + 1] = (uint32_t)dirtyAnn.size();
+  }
+  // identity maps go as null arrays: the kernel then skips their loads (on a
+  // link flap every map but two rows' link_of is the identity)
+  bool sameRows = V == Va, sameCols = C == Ca;
+  for (uint32_t i = 0; sameRows && i < V; ++i) {
+    sameRows = rowOf[i] == i;
+  }
+  for (size_t p = 0; sameCols && p < C; ++p) {
+    sameCols = colOf[p] == p;
+  }
+  spf_route_diff_map m{};
+  m.row_of = sameRows ? nullptr : rowOf.data();
+  m.col_of = sameCols ? nullptr : colOf.data();
+  m.gone_cols = gone.data();
+  m.num_gone = (uint32_t)gone.size();
+  m.node_of = sameRows ? nullptr : nodeOf.data();
+  m.link_off = linkOf.empty() ? nullptr : linkOff.data();
+  m.link_of = linkOf.data();
+  m.dirty_off = dirtyAnn.empty() ? nullptr : dirtyOff.data();
+  m.dirty_ann = dirtyAnn.data();
+  std::vector<uint32_t> changed(V);
+  const auto tp = std::chrono::steady_clock::now();
+  if (int s = spf_route_table_diff_mapped(older.table_, table_, &m, changed.data());
+      s != SPF_OK) {
     if (s == SPF_E_UNSUPPORTED) {
       throw std::invalid_argument(std::string("AllNodesRouteTable::diff: ") +
                                   spf_last_error_detail());
     }
-    tableFailure("spf_route_table_diff", s);
+    tableFailure("spf_route_table_diff_mapped", s);
   }
+  diffCallMs_ = (float)usSince(tp) / 1000.f;
   diffed_ = true;
+  mapped_ = true;
+  rowOf_ = std::move(rowOf);
+  goneCols_ = std::move(gone);
   older_ = &older;
   return changed;
 }
@@ -584,12 +757,14 @@ std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string
   }
   auto it = ids_.find(node);
   const size_t P = prefixes_.size(), C = P + owners_.size();
-  if (it == ids_.end() || !C) {
+  if (it == ids_.end() || (!C && goneCols_.empty())) {
     return {0, 0};
   }
   std::vector<uint64_t> bits((C + 63) / 64);
-  if (int s = spf_route_table_changed(table_, it->second, bits.data()); s != SPF_OK) {
-    tableFailure("spf_route_table_changed", s);
+  if (C) {
+    if (int s = spf_route_table_changed(table_, it->second, bits.data()); s != SPF_OK) {
+      tableFailure("spf_route_table_changed", s);
+    }
   }
   uint32_t uni = 0, lab = 0;
   for (size_t k = 0; k < bits.size(); ++k) {
@@ -598,6 +773,21 @@ std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string
       const size_t p = k * 64 + __builtin_ctzll(m);
       m &= m - 1;
       (p < P ? uni : lab) += 1;
+    }
+  }
+  if (!goneCols_.empty()) {
+    // deleted columns of the older table
+    std::vector<uint64_t> gbits((goneCols_.size() + 63) / 64);
+    if (int s = spf_route_table_changed_gone(table_, it->second, gbits.data()); s != SPF_OK) {
+      tableFailure("spf_route_table_changed_gone", s);
+    }
+    for (size_t k = 0; k < gbits.size(); ++k) {
+      uint64_t m = gbits[k];
+      while (m) {
+        const size_t g = k * 64 + __builtin_ctzll(m);
+        m &= m - 1;
+        (goneCols_[g] < older_->prefixes_.size() ? uni : lab) += 1;
+      }
     }
   }
   return {uni, lab};
@@ -624,13 +814,47 @@ DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
   for (uint64_t b : bits) {
     any |= b != 0;
   }
+  // the node's row in the older table (none: every route here is new)
+  const uint32_t ia = rowOf_[i];
+  const bool hasOld = ia != SPF_MAP_NONE;
+  const size_t Pa = older_->prefixes_.size(), Ca = Pa + older_->owners_.size();
   // MPLS candidates: labels of changed label columns + adjacency labels
   std::set<int32_t> labels;
   for (const AdjLabel& a : adjLabels_[i]) {
     labels.insert(a.label);
   }
-  for (const AdjLabel& a : older_->adjLabels_[i]) {
-    labels.insert(a.label);
+  if (hasOld) {
+    for (const AdjLabel& a : older_->adjLabels_[ia]) {
+      labels.insert(a.label);
+    }
+  }
+  if (mapped_) {
+    // the node's own label: POP_AND_LOOKUP has no cell behind it
+    if (nodeLabel_[i]) {
+      labels.insert(nodeLabel_[i]);
+    }
+    if (hasOld && older_->nodeLabel_[ia]) {
+      labels.insert(older_->nodeLabel_[ia]);
+    }
+    // deleted columns: unicast prefixes go, labels join the candidates
+    if (!goneCols_.empty()) {
+      std::vector<uint64_t> gbits((goneCols_.size() + 63) / 64);
+      if (int s = spf_route_table_changed_gone(table_, i, gbits.data()); s != SPF_OK) {
+        tableFailure("spf_route_table_changed_gone", s);
+      }
+      for (size_t k = 0; k < gbits.size(); ++k) {
+        uint64_t m = gbits[k];
+        while (m) {
+          const uint32_t c = goneCols_[k * 64 + __builtin_ctzll(m)];
+          m &= m - 1;
+          if (c < Pa) {
+            u.unicastRoutesToDelete.push_back(older_->prefixes_[c]);
+          } else {
+            labels.insert(older_->owners_[c - Pa].label);
+          }
+        }
+      }
+    }
   }
   if (!any && labels.empty()) {
     return u;
@@ -651,10 +875,10 @@ DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
     }
   }
   if (!labels.empty()) {
-    const Row o = C ? older_->fetchRow(i) : Row{};
+    const Row o = hasOld && Ca ? older_->fetchRow(ia) : Row{};
     for (const int32_t label : labels) {
       auto ne = mplsEntry(i, r, label);
-      auto oe = older_->mplsEntry(i, o, label);
+      auto oe = hasOld ? older_->mplsEntry(ia, o, label) : std::nullopt;
       if (ne && (!oe || !(*oe == *ne))) {
         u.mplsRoutesToUpdate.push_back(std::move(*ne));
       } else if (!ne && oe) {

@@ -86,21 +86,35 @@ class AllNodesRouteTable {
   std::unordered_map<int32_t, RibMplsEntry> mplsRoutes(const std::string& node) const;
   size_t numLabelColumns() const { return owners_.size(); }
 
-  // Network-wide route delta against an older table over the same graph
-  // layout, prefixes and node labels (spf_route_table_diff): per node (id
-  // order, see nodeName) the number of changed columns -- unicast prefixes
-  // and node-label columns (changedSplit separates them).  Throws
-  // std::invalid_argument when the layouts differ.
+  // Network-wide route delta against an older table: per node of THIS table
+  // (id order, see nodeName) the number of changed columns -- unicast
+  // prefixes and node-label columns, deleted ones included (changedSplit
+  // separates them).  Over the same graph layout, prefixes and node labels
+  // this is spf_route_table_diff.  Otherwise (links down or up, nodes joined
+  // or gone, prefixes announced or withdrawn, labels changed) the tables are
+  // compared through maps (spf_route_table_diff_mapped): rows and best
+  // announcers by node name, unicast columns by prefix, label columns by
+  // (label, owner name), link bits by Link identity -- a link whose next-hop
+  // addresses, interface or area (what materialise reads) differ has no
+  // counterpart, so every route over it is changed -- and announcers whose
+  // PrefixEntry differs are the column's dirty list.  A node the older table
+  // lacks has every route changed.  Throws std::invalid_argument for BGP
+  // columns, different areas or different LFA modes.
   std::vector<uint32_t> diff(const AllNodesRouteTable& older);
   // (changed unicast prefixes, changed node-label columns) of `node` from
-  // the last diff
+  // the last diff; .first == unicast updates + deletes of delta(node)
   std::pair<uint32_t, uint32_t> changedSplit(const std::string& node) const;
-  // getRouteDelta({routes, mplsRoutes}(node), the same of `older`)
-  // (Decision.cpp:47-85) from the last diff: changed routes materialised,
-  // vanished ones deleted.  MPLS candidates are the labels of changed label
-  // columns and the node's adjacency labels, compared entry by entry against
-  // `older` (which must outlive this call).
+  // getRouteDelta({routes, mplsRoutes}(node), the same of `older`; {} for a
+  // node `older` lacks) (Decision.cpp:47-85) from the last diff: changed
+  // routes materialised, vanished ones (gone columns included) deleted.  MPLS
+  // candidates are the labels of changed and gone label columns, the node's
+  // own label and its adjacency labels in both tables, compared entry by
+  // entry against `older` (which must outlive this call).
   DecisionRouteUpdate delta(const std::string& node) const;
+  // wall time of the device diff call inside the last diff() (maps excluded)
+  float diffCallMs() const { return diffCallMs_; }
+  // the last diff() went through the maps
+  bool diffWasMapped() const { return mapped_; }
   const std::string& nodeName(uint32_t id) const { return names_.at(id); }
   // the unicast prefixes the kernel serves (routes() covers exactly these)
   const std::vector<thrift::IpPrefix>& prefixes() const { return prefixes_; }
@@ -163,7 +177,15 @@ class AllNodesRouteTable {
     std::string area;
   };
   std::vector<std::vector<AdjLabel>> adjLabels_;
+  std::vector<int32_t> nodeLabel_; // per node id: its valid node label, else 0
   const AllNodesRouteTable* older_{nullptr};
+  // the last diff(): older row of every node (SPF_MAP_NONE: none) and, when
+  // it went through the maps, the older columns with no counterpart here
+  bool mapped_{false};
+  std::vector<uint32_t> rowOf_;
+  std::vector<uint32_t> goneCols_;
+  float diffCallMs_{0};
+  std::vector<uint32_t> diffMapped(const AllNodesRouteTable& older);
   spf_graph* graph_{nullptr};
   spf_query* query_{nullptr};
   spf_route_table* table_{nullptr};

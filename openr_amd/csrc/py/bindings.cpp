@@ -459,6 +459,8 @@ PYBIND11_MODULE(_openr_spf, m) {
       })
       .def("diff", &AllNodesRouteTable::diff, py::arg("older"), py::keep_alive<1, 2>())
       .def("node_name", &AllNodesRouteTable::nodeName)
+      .def_property_readonly("diff_call_ms", &AllNodesRouteTable::diffCallMs)
+      .def_property_readonly("diff_was_mapped", &AllNodesRouteTable::diffWasMapped)
       .def("changed_split", &AllNodesRouteTable::changedSplit)
       .def("delta", [](const AllNodesRouteTable& t, const std::string& node) {
         // (updated unicast routes as routes() renders them, deleted prefixes)

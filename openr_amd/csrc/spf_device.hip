@@ -6504,6 +6504,180 @@ __global__ __launch_bounds__(256) void spf_route_table_diff_kernel(
   }
 }
 
+// Mapped route-table diff (spf_route_table_diff_mapped): the same delta
+// (getRouteDelta, Decision.cpp:47-85) between tables whose nodes, columns and
+// link layouts differ.  Cell (q, p) of the newer table is compared with cell
+// (row_of[q], col_of[p]) of the older one (kMapNone: no such cell, i.e. no
+// route there).  With a route on both sides the cell changed iff the metric
+// differs, node_of[older best] != newer best, the newer best is in the
+// column's dirty-announcer list, or the link sets differ as sets of links:
+// every set newer bit j must have an image link_of[j] that is set in the older
+// mask, and the older mask must have no other bit (link_of is injective, so
+// counting the images against the older popcount decides that).  LFA tables
+// also compare each set link's metric with the metric of its image.  A cell
+// with no route on both sides is unchanged.
+//
+// Launch shape of spf_route_table_diff_kernel: one workgroup per row, one
+// wave per 64 columns, the ballot is the bitmap word.  ident[q] != 0 marks a
+// row whose links keep their bit positions (same degree, link_of[j] == j):
+// it compares mask words directly, like the kernel above.  Only the other
+// rows stage their link map in LDS (at most kRtStage entries) and permute;
+// the flag is per row, so the branch is uniform over the workgroup.  The
+// older row is read through col_of: with a permuted col_of these are 4-byte
+// gathers inside one older row (metric, best) plus the cell's own mask words,
+// which is accepted here -- a row is P * 4 bytes and stays cache-resident
+// while its workgroup walks it; no transposed copy is made.
+//
+// Gone columns (older columns with no newer counterpart): bit g of row q's
+// second bitmap is set iff the older cell (row_of[q], gone[g]) had a route --
+// the deletes.  count[q] = popcount of both bitmaps.
+constexpr uint32_t kMapNone = 0xFFFFFFFFu;
+struct RouteDiffMapArgs {
+  const uint32_t *ma, *ba, *mb, *bb;       // metric / best: older (a), newer (b)
+  const uint64_t *la, *lb;                 // link masks
+  const uint64_t *lk_off_a, *lk_off_b;     // [rows + 1] mask-word offsets
+  const uint32_t *lma, *lmb;               // LFA per-link metrics (null: not LFA)
+  const uint64_t *lm_off_a, *lm_off_b;
+  const uint32_t* row_of;                  // [nq] or null (identity)
+  const uint32_t* col_of;                  // [P] or null (identity)
+  const uint32_t* gone;                    // [ng]
+  const uint32_t* node_of;                 // [Va] or null (identity)
+  const uint32_t* link_off;                // [nq + 1] (null with link_of)
+  const uint32_t* link_of;
+  const uint32_t* dirty_off;               // [P + 1] or null (no dirty announcers)
+  const uint32_t* dirty_ann;
+  const uint8_t* ident;                    // [nq] identity-links flag
+  const uint32_t* deg_b;                   // [nq] up links of the newer row's source
+  uint32_t P, Pa, Va, nq, pw, ng, gw;
+  uint64_t* bits;                          // [nq * pw]
+  uint64_t* gone_bits;                     // [nq * gw]
+  uint32_t* count;                         // [nq], zeroed
+};
+
+__global__ __launch_bounds__(256) void spf_route_table_diff_mapped_kernel(RouteDiffMapArgs a) {
+  __shared__ uint32_t st_link[kRtStage];
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t P = a.P, Pa = a.Pa;
+  for (uint32_t q = blockIdx.x; q < a.nq; q += gridDim.x) {
+    const uint32_t qa = a.row_of ? a.row_of[q] : q;
+    const bool ident = a.ident[q] != 0;
+    const uint32_t deg = a.deg_b[q];
+    const uint32_t WLb = P ? (uint32_t)((a.lk_off_b[q + 1] - a.lk_off_b[q]) / P) : 0;
+    uint32_t WLa = 0, dega = 0;
+    const uint64_t *la_q = nullptr, *lb_q = a.lb + a.lk_off_b[q];
+    const uint32_t *lma_q = nullptr, *lmb_q = nullptr;
+    if (qa != kMapNone && Pa) {
+      WLa = (uint32_t)((a.lk_off_a[qa + 1] - a.lk_off_a[qa]) / Pa);
+      la_q = a.la + a.lk_off_a[qa];
+      if (a.lma) {
+        dega = (uint32_t)((a.lm_off_a[qa + 1] - a.lm_off_a[qa]) / Pa);
+        lma_q = a.lma + a.lm_off_a[qa];
+        lmb_q = a.lmb + a.lm_off_b[q];
+      }
+    }
+    if (!ident && qa != kMapNone) { // uniform over the workgroup
+      __syncthreads();              // the previous row's readers are done
+      const uint32_t* lo = a.link_of + a.link_off[q];
+      for (uint32_t j = threadIdx.x; j < deg && j < kRtStage; j += blockDim.x) {
+        st_link[j] = lo[j];
+      }
+      __syncthreads();
+    }
+    uint32_t n = 0;
+    for (uint32_t w = wv; w < a.pw; w += blockDim.x / 64) {
+      const uint32_t p = w * 64 + lane;
+      bool ch = false;
+      if (p < P) {
+        const size_t ob = (size_t)q * P + p;
+        const uint32_t mb = a.mb[ob];
+        const uint32_t pa = qa == kMapNone ? kMapNone : a.col_of ? a.col_of[p] : p;
+        if (pa == kMapNone) {
+          ch = mb != kInf32;
+        } else {
+          const size_t oa = (size_t)qa * Pa + pa;
+          const uint64_t* lac = la_q + (size_t)pa * WLa;
+          const uint64_t* lbc = lb_q + (size_t)p * WLb;
+          // every load of the common case is issued before the first branch
+          // (metric, best and the first mask word of both cells), as the
+          // equal-layout kernel's compare does: dependent rounds of loads
+          // would make the row walk latency-bound
+          const uint32_t ma = a.ma[oa], ba = a.ba[oa], bb = a.bb[ob];
+          const uint64_t la0 = WLa ? lac[0] : 0, lb0 = WLb ? lbc[0] : 0;
+          if (ma == kInf32 || mb == kInf32) {
+            ch = ma != mb;
+          } else {
+            const uint32_t bi = a.node_of ? (ba < a.Va ? a.node_of[ba] : kMapNone) : ba;
+            ch = ma != mb || bi != bb;
+            if (a.dirty_off && !ch) {
+              for (uint32_t i = a.dirty_off[p], e = a.dirty_off[p + 1]; i < e && !ch; ++i) {
+                ch = a.dirty_ann[i] == bb;
+              }
+            }
+            if (ident) {
+              // same bit positions: word compare, then the set links' metrics
+              ch = ch || la0 != lb0;
+              for (uint32_t k = 1; k < WLb && !ch; ++k) {
+                ch = lac[k] != lbc[k];
+              }
+              if (lma_q && !ch) {
+                const uint32_t* xa = lma_q + (size_t)pa * dega;
+                const uint32_t* xb = lmb_q + (size_t)p * deg;
+                for (uint32_t k = 0; k < WLb && !ch; ++k) {
+                  uint64_t m = lbc[k];
+                  while (m && !ch) {
+                    const uint32_t j = k * 64 + (uint32_t)__builtin_ctzll(m);
+                    m &= m - 1;
+                    ch = xa[j] != xb[j];
+                  }
+                }
+              }
+            } else if (!ch) {
+              uint32_t images = 0, olds = 0;
+              for (uint32_t k = 0; k < WLa; ++k) {
+                olds += __popcll(lac[k]);
+              }
+              for (uint32_t k = 0; k < WLb && !ch; ++k) {
+                uint64_t m = lbc[k];
+                while (m && !ch) {
+                  const uint32_t j = k * 64 + (uint32_t)__builtin_ctzll(m);
+                  m &= m - 1;
+                  const uint32_t t = j < kRtStage ? st_link[j] : kMapNone;
+                  if (t == kMapNone || t >= WLa * 64 || !((lac[t >> 6] >> (t & 63)) & 1ull)) {
+                    ch = true;
+                  } else {
+                    ++images;
+                    if (lma_q) {
+                      ch = lma_q[(size_t)pa * dega + t] != lmb_q[(size_t)p * deg + j];
+                    }
+                  }
+                }
+              }
+              ch = ch || images != olds;
+            }
+          }
+        }
+      }
+      const uint64_t word = __ballot(ch);
+      if (lane == 0) {
+        a.bits[(size_t)q * a.pw + w] = word;
+        n += __popcll(word);
+      }
+    }
+    for (uint32_t w = wv; w < a.gw; w += blockDim.x / 64) {
+      const uint32_t g = w * 64 + lane;
+      const bool had = g < a.ng && qa != kMapNone && a.ma[(size_t)qa * Pa + a.gone[g]] != kInf32;
+      const uint64_t word = __ballot(had);
+      if (lane == 0) {
+        a.gone_bits[(size_t)q * a.gw + w] = word;
+        n += __popcll(word);
+      }
+    }
+    if (lane == 0 && n) {
+      atomicAdd(&a.count[q], n);
+    }
+  }
+}
+
 // ------------------------------------------------ k-th path traces (KSP2)
 //
 // getKthPaths' trace loop (LinkState.cpp:776-786) over one query row: repeated
@@ -13928,6 +14102,15 @@ struct spf_route_table {
   uint64_t* d_lm_off = nullptr;
   uint32_t* d_lmet = nullptr;
   int32_t* d_row_of = nullptr;
+  // spf_route_table_diff_mapped: up links of every row's source, the staged
+  // maps and the gone-column bitmap of the last mapped diff
+  std::vector<uint32_t> deg; // [nq]
+  uint32_t* d_map = nullptr;
+  size_t map_cap = 0; // uint32 words
+  uint64_t* d_gone = nullptr;
+  size_t gone_cap = 0; // uint64 words
+  uint32_t gone_n = 0;
+  bool mapped = false;
 };
 
 namespace {
@@ -13939,7 +14122,8 @@ void free_route_table(spf_route_table* t) {
   t->q->live_tables.fetch_sub(1, std::memory_order_relaxed);
   for (void* p : {(void*)t->d_ann_off, (void*)t->d_ann, (void*)t->d_metric, (void*)t->d_best,
                   (void*)t->d_lk_off, (void*)t->d_links, (void*)t->d_diff, (void*)t->d_count,
-                  (void*)t->d_lm_off, (void*)t->d_lmet, (void*)t->d_row_of}) {
+                  (void*)t->d_lm_off, (void*)t->d_lmet, (void*)t->d_row_of, (void*)t->d_map,
+                  (void*)t->d_gone}) {
     if (p) {
       (void)hipFree(p);
     }
@@ -14026,8 +14210,10 @@ int spf_route_table_create_ex(
   t->lfa = lfa;
   t->lk_off.assign(q->nq + 1, 0);
   t->lm_off.assign(q->nq + 1, 0);
+  t->deg.assign(q->nq, 0);
   for (uint32_t i = 0; i < q->nq; ++i) {
     const uint32_t deg = g->row[src[i] + 1] - g->row[src[i]];
+    t->deg[i] = deg;
     t->lk_off[i + 1] = t->lk_off[i] + (uint64_t)num_prefixes * ((deg + 63) / 64);
     t->lm_off[i + 1] = t->lm_off[i] + (lfa ? (uint64_t)num_prefixes * deg : 0);
   }
@@ -14257,6 +14443,256 @@ int spf_route_table_changed(spf_route_table* t, uint32_t i, uint64_t* bits) {
   HIP_TRY(hipSetDevice(t->q->g->device));
   HIP_TRY(hipStreamSynchronize(t->q->g->stream));
   HIP_TRY(hipMemcpy(bits, t->d_diff + (size_t)i * pw, (size_t)pw * 8, hipMemcpyDeviceToHost));
+  return SPF_OK;
+}
+
+int spf_route_table_diff_mapped(
+    spf_route_table* older, spf_route_table* newer, const spf_route_diff_map* map,
+    uint32_t* changed) {
+  SPF_ABI_RANGE("spf_route_table_diff_mapped");
+  if (!older || !newer || (newer->q->nq && !changed)) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  if (!older->ran || !newer->ran) {
+    return fail(SPF_E_INVALID, "both tables must have run");
+  }
+  static const spf_route_diff_map kIdentity{};
+  const spf_route_diff_map& m = map ? *map : kIdentity;
+  const spf_graph* ga = older->q->g;
+  spf_graph* gb = newer->q->g;
+  if (ga->device != gb->device || older->lfa != newer->lfa) {
+    return fail(SPF_E_UNSUPPORTED, "tables differ in SPF_RT_LFA or in device");
+  }
+  const uint32_t nq = newer->q->nq, nqa = older->q->nq, P = newer->P, Pa = older->P;
+  const uint32_t Va = ga->V, Vb = gb->V, ng = m.num_gone;
+  const uint32_t pw = (P + 63) / 64, gw = (ng + 63) / 64;
+  // ---- validation (host): every index the kernel follows is in range
+  if (!m.row_of && nq > nqa) {
+    return fail(SPF_E_INVALID, "null row_of (identity) with more newer rows than older rows");
+  }
+  for (uint32_t i = 0; m.row_of && i < nq; ++i) {
+    if (m.row_of[i] != SPF_MAP_NONE && m.row_of[i] >= nqa) {
+      return fail(SPF_E_INVALID, "row_of entry out of range");
+    }
+  }
+  if (!m.col_of && P > Pa) {
+    return fail(SPF_E_INVALID, "null col_of (identity) with more newer columns than older columns");
+  }
+  if (m.col_of) {
+    std::vector<uint8_t> seen(Pa, 0);
+    for (uint32_t p = 0; p < P; ++p) {
+      const uint32_t c = m.col_of[p];
+      if (c == SPF_MAP_NONE) {
+        continue;
+      }
+      if (c >= Pa) {
+        return fail(SPF_E_INVALID, "col_of entry out of range");
+      }
+      if (seen[c]) {
+        return fail(SPF_E_INVALID, "col_of maps two columns to the same older column");
+      }
+      seen[c] = 1;
+    }
+  }
+  if (ng && !m.gone_cols) {
+    return fail(SPF_E_INVALID, "null gone_cols");
+  }
+  for (uint32_t g = 0; g < ng; ++g) {
+    if (m.gone_cols[g] >= Pa) {
+      return fail(SPF_E_INVALID, "gone_cols entry out of range");
+    }
+  }
+  for (uint32_t v = 0; m.node_of && v < Va; ++v) {
+    if (m.node_of[v] != SPF_MAP_NONE && m.node_of[v] >= Vb) {
+      return fail(SPF_E_INVALID, "node_of entry out of range");
+    }
+  }
+  const uint32_t nlink = m.link_off ? m.link_off[nq] : 0;
+  if (m.link_off && m.link_off[0] != 0) {
+    return fail(SPF_E_INVALID, "link_off[0] != 0");
+  }
+  if (nlink && !m.link_of) {
+    return fail(SPF_E_INVALID, "null link_of");
+  }
+  std::vector<uint8_t> ident(((size_t)nq + 3) & ~(size_t)3, 1);
+  {
+    std::vector<uint8_t> seen;
+    for (uint32_t i = 0; i < nq; ++i) {
+      const uint32_t lo = m.link_off ? m.link_off[i] : 0, hi = m.link_off ? m.link_off[i + 1] : 0;
+      if (hi < lo) {
+        return fail(SPF_E_INVALID, "link_off not monotone");
+      }
+      const uint32_t qa = m.row_of ? m.row_of[i] : i;
+      const uint32_t deg = newer->deg[i];
+      if (hi != lo && hi - lo != deg) {
+        return fail(SPF_E_INVALID, "a row's link_of segment is neither empty nor its link count");
+      }
+      if (qa == SPF_MAP_NONE) {
+        continue;
+      }
+      const uint32_t dega = older->deg[qa];
+      if (hi == lo) { // identity: the bit positions must be the same links
+        if (deg != dega) {
+          return fail(SPF_E_INVALID, "identity link map over rows with different link counts");
+        }
+        continue;
+      }
+      bool same = deg == dega;
+      seen.assign(dega, 0);
+      for (uint32_t j = 0; j < deg; ++j) {
+        const uint32_t t = m.link_of[lo + j];
+        same = same && t == j;
+        if (t == SPF_MAP_NONE) {
+          continue;
+        }
+        if (t >= dega) {
+          return fail(SPF_E_INVALID, "link_of entry out of range");
+        }
+        if (seen[t]) {
+          return fail(SPF_E_INVALID, "link_of maps two links to the same older link");
+        }
+        seen[t] = 1;
+      }
+      if (!same && deg > kRtStage) {
+        return fail(SPF_E_UNSUPPORTED, "a remapped link row with more than 1024 links");
+      }
+      ident[i] = same ? 1 : 0;
+    }
+  }
+  uint32_t nd = 0;
+  if (m.dirty_off) {
+    if (m.dirty_off[0] != 0) {
+      return fail(SPF_E_INVALID, "dirty_off[0] != 0");
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+      if (m.dirty_off[p + 1] < m.dirty_off[p]) {
+        return fail(SPF_E_INVALID, "dirty_off not monotone");
+      }
+    }
+    nd = m.dirty_off[P];
+    if (nd && !m.dirty_ann) {
+      return fail(SPF_E_INVALID, "null dirty_ann");
+    }
+    for (uint32_t i = 0; i < nd; ++i) {
+      if (m.dirty_ann[i] >= Vb) {
+        return fail(SPF_E_INVALID, "dirty_ann entry out of range");
+      }
+    }
+  }
+  newer->gone_n = ng;
+  newer->mapped = true;
+  if (nq == 0) {
+    return SPF_OK;
+  }
+  // ---- one staging buffer of uint32 words for every map the kernel reads
+  std::vector<uint32_t> stage;
+  auto put = [&](const uint32_t* p, size_t n) {
+    const size_t at = stage.size();
+    stage.insert(stage.end(), p, p + n);
+    return at;
+  };
+  const size_t o_deg = put(newer->deg.data(), nq);
+  const size_t o_ident = put((const uint32_t*)ident.data(), ident.size() / 4);
+  const size_t o_row = m.row_of ? put(m.row_of, nq) : 0;
+  const size_t o_col = m.col_of ? put(m.col_of, P) : 0;
+  const size_t o_gone = ng ? put(m.gone_cols, ng) : 0;
+  const size_t o_node = m.node_of ? put(m.node_of, Va) : 0;
+  const size_t o_loff = m.link_off ? put(m.link_off, (size_t)nq + 1) : 0;
+  const size_t o_lof = nlink ? put(m.link_of, nlink) : 0;
+  const size_t o_doff = m.dirty_off ? put(m.dirty_off, (size_t)P + 1) : 0;
+  const size_t o_dann = nd ? put(m.dirty_ann, nd) : 0;
+  HIP_TRY(hipSetDevice(gb->device));
+  if (!newer->d_count) {
+    HIP_TRY(hipMalloc((void**)&newer->d_count, (size_t)nq * 4));
+    if (pw) {
+      HIP_TRY(hipMalloc((void**)&newer->d_diff, (size_t)nq * pw * 8));
+    }
+  }
+  if (stage.size() > newer->map_cap) {
+    if (newer->d_map) {
+      (void)hipFree(newer->d_map);
+      newer->d_map = nullptr;
+      newer->map_cap = 0;
+    }
+    HIP_TRY(hipMalloc((void**)&newer->d_map, stage.size() * 4));
+    newer->map_cap = stage.size();
+  }
+  if ((size_t)nq * gw > newer->gone_cap) {
+    if (newer->d_gone) {
+      (void)hipFree(newer->d_gone);
+      newer->d_gone = nullptr;
+      newer->gone_cap = 0;
+    }
+    HIP_TRY(hipMalloc((void**)&newer->d_gone, (size_t)nq * gw * 8));
+    newer->gone_cap = (size_t)nq * gw;
+  }
+  // the older table's rows are read on the newer table's stream
+  HIP_TRY(hipStreamSynchronize(ga->stream));
+  HIP_TRY(hipMemcpyAsync(newer->d_map, stage.data(), stage.size() * 4, hipMemcpyHostToDevice,
+                         gb->stream));
+  HIP_TRY(hipMemsetAsync(newer->d_count, 0, (size_t)nq * 4, gb->stream));
+  if (P || ng) {
+    RouteDiffMapArgs a{};
+    const uint32_t* d = newer->d_map;
+    a.ma = older->d_metric;
+    a.ba = older->d_best;
+    a.la = older->d_links;
+    a.mb = newer->d_metric;
+    a.bb = newer->d_best;
+    a.lb = newer->d_links;
+    a.lk_off_a = older->d_lk_off;
+    a.lk_off_b = newer->d_lk_off;
+    a.lma = older->d_lmet;
+    a.lmb = newer->d_lmet;
+    a.lm_off_a = older->d_lm_off;
+    a.lm_off_b = newer->d_lm_off;
+    a.deg_b = d + o_deg;
+    a.ident = (const uint8_t*)(d + o_ident);
+    a.row_of = m.row_of ? d + o_row : nullptr;
+    a.col_of = m.col_of ? d + o_col : nullptr;
+    a.gone = ng ? d + o_gone : nullptr;
+    a.node_of = m.node_of ? d + o_node : nullptr;
+    a.link_off = m.link_off ? d + o_loff : nullptr;
+    a.link_of = nlink ? d + o_lof : nullptr;
+    a.dirty_off = m.dirty_off ? d + o_doff : nullptr;
+    a.dirty_ann = nd ? d + o_dann : nullptr;
+    a.P = P;
+    a.Pa = Pa;
+    a.Va = Va;
+    a.nq = nq;
+    a.pw = pw;
+    a.ng = ng;
+    a.gw = gw;
+    a.bits = newer->d_diff;
+    a.gone_bits = newer->d_gone;
+    a.count = newer->d_count;
+    const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)gb->num_cus * 8);
+    SPF_LAUNCH(spf_route_table_diff_mapped_kernel, dim3(grid), dim3(256), 0, gb->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(changed, newer->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost,
+                         gb->stream));
+  HIP_TRY(hipStreamSynchronize(gb->stream));
+  return SPF_OK;
+}
+
+int spf_route_table_changed_gone(spf_route_table* t, uint32_t i, uint64_t* bits) {
+  if (!t || i >= t->q->nq) {
+    return fail(SPF_E_INVALID, "bad argument");
+  }
+  if (!t->mapped) {
+    return fail(SPF_E_INVALID, "no mapped diff has run on this table");
+  }
+  const uint32_t gw = (t->gone_n + 63) / 64;
+  if (!gw) {
+    return SPF_OK;
+  }
+  if (!bits) {
+    return fail(SPF_E_INVALID, "null bits");
+  }
+  HIP_TRY(hipSetDevice(t->q->g->device));
+  HIP_TRY(hipStreamSynchronize(t->q->g->stream));
+  HIP_TRY(hipMemcpy(bits, t->d_gone + (size_t)i * gw, (size_t)gw * 8, hipMemcpyDeviceToHost));
   return SPF_OK;
 }
 
