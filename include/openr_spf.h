@@ -494,6 +494,49 @@ int spf_route_table_diff_mapped(
  * row had a route in gone_cols[g]; bits[ceil(num_gone/64)]. */
 int spf_route_table_changed_gone(spf_route_table* t, uint32_t i, uint64_t* bits);
 
+/* The delta itself (getRouteDelta, Decision.cpp:47-85: the updates and
+ * deletes, not their number) of every node as one record list built on the
+ * device: the changed cells of the last diff, compacted out of the bitmaps,
+ * so that a consumer copies the cells that changed and not two whole rows per
+ * node.  Compute on the device, then fetch (as spf_query_trace_paths /
+ * _trace_fetch). */
+typedef struct spf_route_delta_sizes {
+  uint64_t cells;        /* changed cells of `newer` over all rows */
+  uint64_t gone;         /* deleted gone-column entries over all rows */
+  uint64_t link_words;   /* sum over changed cells of link_words(row) */
+  uint64_t link_metrics; /* SPF_RT_LFA: sum over changed cells of deg(row); else 0 */
+} spf_route_delta_sizes;
+/* After spf_route_table_diff or _diff_mapped on `newer`: build, on the device,
+ * the list of its changed cells.  Rows ascending; columns ascending within a
+ * row.  The values are copies taken from `newer` alone (`older` is not needed
+ * after the call); the buffers belong to the table and only grow.  After an
+ * equal-layout diff `gone` is 0.  SPF_E_INVALID before any diff (or after a
+ * later spf_route_table_run with no diff since); zero changed cells is
+ * SPF_OK with all sizes 0.  Synchronises the graph stream once. */
+int spf_route_table_delta_pack(spf_route_table* newer, spf_route_delta_sizes* sizes);
+/* The packed list to host.  Cell k of row i has cell_off[i] <= k <
+ * cell_off[i+1]; its link words start at sum over r<i of (cell_off[r+1] -
+ * cell_off[r]) * link_words(r) + (k - cell_off[i]) * link_words(i), its link
+ * metrics (SPF_RT_LFA) at the same sum with deg(row) in place of link_words
+ * (a row without up links has cells and no link words).  gone[] holds indices
+ * g into the diff's gone_cols, row i's in gone_off[i] .. gone_off[i+1].
+ * SPF_E_INVALID before a pack, or when the table ran or diffed since (the
+ * pack is stale). */
+int spf_route_table_delta_fetch(
+    spf_route_table* newer,
+    uint64_t* cell_off /*[rows+1]*/, uint32_t* col, uint32_t* metric, uint32_t* best /*[cells]*/,
+    uint64_t* links /*[link_words]*/, uint32_t* link_metrics /*[link_metrics], NULL unless LFA*/,
+    uint64_t* gone_off /*[rows+1]*/, uint32_t* gone /*[gone]: index g into gone_cols*/);
+/* Sparse read of any run table: cell k = (rows[k], cols[k]) (repeats allowed).
+ * Links and link metrics are packed in list order, link_words(rows[k]) /
+ * deg(rows[k]) each (link_metrics: SPF_RT_LFA tables only, else NULL).  What
+ * getRouteDelta's MPLS side needs of a column that did not change.  Rows and
+ * columns are checked on the host before any launch (SPF_E_INVALID); n = 0 is
+ * SPF_OK. */
+int spf_route_table_fetch_cells(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols,
+    uint32_t* metric, uint32_t* best, uint64_t* links, uint32_t* link_metrics);
+
 /* ---- multi-GPU all-sources tables ----
  * The reference computes every SpfResult on the one Decision thread
  * (getSpfResult, LinkState.cpp:791-801; all sources = Decision::

@@ -93,6 +93,9 @@ EXPORTED_SYMBOLS = (
     "spf_route_table_changed",
     "spf_route_table_diff_mapped",
     "spf_route_table_changed_gone",
+    "spf_route_table_delta_pack",
+    "spf_route_table_delta_fetch",
+    "spf_route_table_fetch_cells",
     "spf_cluster_unique_id",
     "spf_cluster_create_local",
     "spf_cluster_create_rank",
@@ -244,6 +247,15 @@ class _RouteDiffMap(C.Structure):
     ]
 
 
+class _RouteDeltaSizes(C.Structure):
+    _fields_ = [
+        ("cells", C.c_uint64),
+        ("gone", C.c_uint64),
+        ("link_words", C.c_uint64),
+        ("link_metrics", C.c_uint64),
+    ]
+
+
 def _route_diff_map(row_of=None, col_of=None, gone_cols=None, node_of=None, link_off=None,
                     link_of=None, dirty_off=None, dirty_ann=None):
     """(spf_route_diff_map, arrays it points into); None stays a null array
@@ -387,6 +399,11 @@ def load():
         "spf_route_table_changed": (C.c_int, [vp, u32, pu64]),
         "spf_route_table_diff_mapped": (C.c_int, [vp, vp, C.POINTER(_RouteDiffMap), pu32]),
         "spf_route_table_changed_gone": (C.c_int, [vp, u32, pu64]),
+        "spf_route_table_delta_pack": (C.c_int, [vp, C.POINTER(_RouteDeltaSizes)]),
+        "spf_route_table_delta_fetch": (C.c_int, [vp, pu64, pu32, pu32, pu32, pu64, pu32, pu64,
+                                                  pu32]),
+        "spf_route_table_fetch_cells": (C.c_int, [vp, C.c_uint64, pu32, pu32, pu32, pu32, pu64,
+                                                  pu32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
@@ -993,6 +1010,60 @@ class RouteTable:
         _check(load().spf_route_table_changed_gone(self.h, i, _p(bits, C.c_uint64)),
                "spf_route_table_changed_gone")
         return np.unpackbits(bits.view(np.uint8), bitorder="little")[: self.num_gone].astype(bool)
+
+    def delta_pack(self) -> dict:
+        """spf_route_table_delta_pack + _delta_fetch: the changed cells of the
+        last diff as numpy arrays (cell_off, col, metric, best, links,
+        link_metrics, gone_off, gone) plus the four sizes."""
+        z = _RouteDeltaSizes()
+        _check(load().spf_route_table_delta_pack(self.h, C.byref(z)), "spf_route_table_delta_pack")
+        return self.delta_fetch(z)
+
+    def delta_fetch(self, z) -> dict:
+        """spf_route_table_delta_fetch into arrays sized by `z` (the sizes the
+        pack returned)."""
+        cell_off = np.zeros(self.n + 1, dtype=np.uint64)
+        gone_off = np.zeros(self.n + 1, dtype=np.uint64)
+        col = np.zeros(max(z.cells, 1), dtype=np.uint32)
+        metric = np.zeros(max(z.cells, 1), dtype=np.uint32)
+        best = np.zeros(max(z.cells, 1), dtype=np.uint32)
+        links = np.zeros(max(z.link_words, 1), dtype=np.uint64)
+        lmet = np.zeros(max(z.link_metrics, 1), dtype=np.uint32)
+        gone = np.zeros(max(z.gone, 1), dtype=np.uint32)
+        _check(load().spf_route_table_delta_fetch(
+            self.h, _p(cell_off, C.c_uint64), _p(col, C.c_uint32), _p(metric, C.c_uint32),
+            _p(best, C.c_uint32), _p(links, C.c_uint64),
+            _p(lmet, C.c_uint32) if self.lfa else None, _p(gone_off, C.c_uint64),
+            _p(gone, C.c_uint32)), "spf_route_table_delta_fetch")
+        return {
+            "cells": int(z.cells), "num_gone": int(z.gone), "link_words": int(z.link_words),
+            "num_link_metrics": int(z.link_metrics),
+            "cell_off": cell_off, "col": col[: z.cells], "metric": metric[: z.cells],
+            "best": best[: z.cells], "links": links[: z.link_words],
+            "link_metrics": lmet[: z.link_metrics], "gone_off": gone_off, "gone": gone[: z.gone],
+        }
+
+    def fetch_cells(self, rows, cols, degs=None):
+        """spf_route_table_fetch_cells: (metric [n], best [n], links, link
+        metrics) of the cells (rows[k], cols[k]); links are packed in list
+        order, link_words(rows[k]) words each, link metrics (SPF_RT_LFA, needs
+        `degs`: up links per table row) degs[rows[k]] each."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        n = len(rows)
+        assert len(cols) == n
+        in_range = rows[rows < self.n]
+        nl = sum(self.link_words(int(r)) for r in in_range)
+        nm = int(sum(int(degs[int(r)]) for r in in_range)) if self.lfa else 0
+        metric = np.zeros(max(n, 1), dtype=np.uint32)
+        best = np.zeros(max(n, 1), dtype=np.uint32)
+        links = np.zeros(max(nl, 1), dtype=np.uint64)
+        lmet = np.zeros(max(nm, 1), dtype=np.uint32)
+        _check(load().spf_route_table_fetch_cells(
+            self.h, n, _p(rows, C.c_uint32) if n else None, _p(cols, C.c_uint32) if n else None,
+            _p(metric, C.c_uint32), _p(best, C.c_uint32), _p(links, C.c_uint64),
+            _p(lmet, C.c_uint32) if self.lfa else None), "spf_route_table_fetch_cells")
+        return metric[:n], best[:n], links[:nl], lmet[:nm]
 
 
 # ------------------------------------------------- multi-GPU tables (RCCL)

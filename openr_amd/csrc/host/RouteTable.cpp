@@ -426,8 +426,9 @@ RibUnicastEntry AllNodesRouteTable::materialise(
   const bool isV4 = prefixes_[p].prefixAddress.addr.size() == 4;
   const uint32_t e0 = row_[i];
   std::unordered_set<thrift::NextHopThrift> nhs;
+  const uint64_t* mask = r.W ? r.linksOf(p) : nullptr;
   for (size_t k = 0; k < r.W; ++k) {
-    uint64_t m = r.links[p * r.W + k];
+    uint64_t m = mask[k];
     while (m) {
       const uint32_t j = (uint32_t)(k * 64 + __builtin_ctzll(m));
       m &= m - 1;
@@ -445,7 +446,7 @@ RibUnicastEntry AllNodesRouteTable::materialise(
   }
   const thrift::PrefixEntry* bestEntry = nullptr;
   for (const auto& a : announcers_[p]) {
-    if (a.id == r.best[p]) {
+    if (a.id == r.bestOf(p)) {
       bestEntry = &a.entry;
     }
   }
@@ -464,7 +465,7 @@ std::unordered_map<thrift::IpPrefix, RibUnicastEntry> AllNodesRouteTable::routes
   }
   const Row r = fetchRow(it->second);
   for (size_t p = 0; p < prefixes_.size(); ++p) {
-    if (r.metric[p] != 0xFFFFFFFFu) {
+    if (r.metricOf(p) != 0xFFFFFFFFu) {
       out.emplace(prefixes_[p], materialise(node, it->second, r, p));
     }
   }
@@ -488,15 +489,16 @@ std::optional<RibMplsEntry> AllNodesRouteTable::nodeLabelEntry(
       nh.mplsAction = createMplsAction(thrift::MplsActionCode::POP_AND_LOOKUP);
       return RibMplsEntry(label, {nh});
     }
-    if (r.metric[col] == 0xFFFFFFFFu) {
+    if (r.metricOf(col) == 0xFFFFFFFFu) {
       continue;
     }
     const std::string& node = names_[i];
     const std::string& owner = names_[o.id];
     const uint32_t e0 = row_[i];
     std::unordered_set<thrift::NextHopThrift> nhs;
+    const uint64_t* mask = r.W ? r.linksOf(col) : nullptr;
     for (size_t k = 0; k < r.W; ++k) {
-      uint64_t m = r.links[col * r.W + k];
+      uint64_t m = mask[k];
       while (m) {
         const uint32_t j = (uint32_t)(k * 64 + __builtin_ctzll(m));
         m &= m - 1;
@@ -867,7 +869,7 @@ DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
       m &= m - 1;
       if (p >= P) {
         labels.insert(owners_[p - P].label);
-      } else if (r.metric[p] == 0xFFFFFFFFu) {
+      } else if (r.metricOf(p) == 0xFFFFFFFFu) {
         u.unicastRoutesToDelete.push_back(prefixes_[p]);
       } else {
         u.unicastRoutesToUpdate.push_back(materialise(node, i, r, p));
@@ -887,6 +889,255 @@ DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
     }
   }
   return u;
+}
+
+uint64_t AllNodesRouteTable::deltaFetchBytes(const std::string& node) const {
+  auto it = ids_.find(node);
+  if (!diffed_ || it == ids_.end()) {
+    return 0;
+  }
+  const uint32_t i = it->second;
+  auto rowBytes = [](const AllNodesRouteTable& t, uint32_t r) {
+    const uint64_t C = t.prefixes_.size() + t.owners_.size();
+    const uint64_t deg = t.row_[r + 1] - t.row_[r];
+    return C * (8 + ((deg + 63) / 64) * 8 + (t.lfa_ ? deg * 4 : 0));
+  };
+  const uint64_t C = prefixes_.size() + owners_.size();
+  uint64_t b = ((C + 63) / 64) * 8 + rowBytes(*this, i);
+  if (mapped_ && !goneCols_.empty()) {
+    b += ((goneCols_.size() + 63) / 64) * 8;
+  }
+  if (rowOf_[i] != SPF_MAP_NONE) {
+    b += rowBytes(*older_, rowOf_[i]);
+  }
+  return b;
+}
+
+std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
+  if (!diffed_) {
+    throw std::logic_error("AllNodesRouteTable::deltas: no diff has run");
+  }
+  using Clock = std::chrono::steady_clock;
+  auto us = [](Clock::time_point a, Clock::time_point b) {
+    return std::chrono::duration<double, std::micro>(b - a).count();
+  };
+  const auto t0 = Clock::now();
+  const uint32_t V = (uint32_t)names_.size();
+  const size_t P = prefixes_.size();
+  const size_t Pa = older_->prefixes_.size();
+  std::vector<DecisionRouteUpdate> out(V);
+  DeltasStats st;
+
+  // ---- the changed cells of every row, compacted on the device
+  spf_route_delta_sizes z{};
+  if (int s = spf_route_table_delta_pack(table_, &z); s != SPF_OK) {
+    tableFailure("spf_route_table_delta_pack", s);
+  }
+  const auto t1 = Clock::now();
+  std::vector<uint64_t> cellOff((size_t)V + 1), goneOff((size_t)V + 1);
+  std::vector<uint32_t> col(z.cells), metric(z.cells), best(z.cells), gone(z.gone);
+  std::vector<uint64_t> links(z.link_words);
+  std::vector<uint32_t> lmet(z.link_metrics);
+  if (int s = spf_route_table_delta_fetch(
+          table_, cellOff.data(), col.data(), metric.data(), best.data(), links.data(),
+          lfa_ ? lmet.data() : nullptr, goneOff.data(), gone.data());
+      s != SPF_OK) {
+    tableFailure("spf_route_table_delta_fetch", s);
+  }
+  const auto t2 = Clock::now();
+  auto degOf = [](const AllNodesRouteTable& t, uint32_t r) {
+    return (size_t)(t.row_[r + 1] - t.row_[r]);
+  };
+  // link-word and link-metric base of every row's cells in the packed list
+  std::vector<uint64_t> lwBase((size_t)V + 1, 0), lmBase((size_t)V + 1, 0);
+  for (uint32_t i = 0; i < V; ++i) {
+    const uint64_t n = cellOff[i + 1] - cellOff[i], deg = degOf(*this, i);
+    lwBase[i + 1] = lwBase[i] + n * ((deg + 63) / 64);
+    lmBase[i + 1] = lmBase[i] + (lfa_ ? n * deg : 0);
+  }
+
+  // ---- MPLS candidates of every node (the labels delta() compares) and the
+  // cells mplsEntry reads for them: every column of the label, in both tables
+  std::vector<std::vector<int32_t>> labelsOf(V);
+  std::vector<std::vector<uint32_t>> colsN(V), colsO(V);
+  const unsigned threads = hostThreads(V, 64);
+  parallelFor(V, threads, [&](size_t n, unsigned) {
+    const uint32_t i = (uint32_t)n;
+    const uint32_t ia = rowOf_[i];
+    const bool hasOld = ia != SPF_MAP_NONE;
+    std::set<int32_t> labels;
+    for (const AdjLabel& a : adjLabels_[i]) {
+      labels.insert(a.label);
+    }
+    if (hasOld) {
+      for (const AdjLabel& a : older_->adjLabels_[ia]) {
+        labels.insert(a.label);
+      }
+    }
+    if (mapped_) {
+      if (nodeLabel_[i]) {
+        labels.insert(nodeLabel_[i]);
+      }
+      if (hasOld && older_->nodeLabel_[ia]) {
+        labels.insert(older_->nodeLabel_[ia]);
+      }
+      for (uint64_t k = goneOff[i]; k < goneOff[i + 1]; ++k) {
+        const uint32_t c = goneCols_[gone[k]];
+        if (c >= Pa) {
+          labels.insert(older_->owners_[c - Pa].label);
+        }
+      }
+    }
+    for (uint64_t k = cellOff[i]; k < cellOff[i + 1]; ++k) {
+      if (col[k] >= P) {
+        labels.insert(owners_[col[k] - P].label);
+      }
+    }
+    for (const int32_t label : labels) {
+      if (auto lc = labelCols_.find(label); lc != labelCols_.end()) {
+        colsN[i].insert(colsN[i].end(), lc->second.begin(), lc->second.end());
+      }
+      if (hasOld) {
+        if (auto lc = older_->labelCols_.find(label); lc != older_->labelCols_.end()) {
+          colsO[i].insert(colsO[i].end(), lc->second.begin(), lc->second.end());
+        }
+      }
+    }
+    std::sort(colsN[i].begin(), colsN[i].end());
+    std::sort(colsO[i].begin(), colsO[i].end());
+    labelsOf[i].assign(labels.begin(), labels.end());
+  });
+
+  // ---- one sparse read per table
+  struct Cells {
+    std::vector<uint64_t> off, lwPos, lmPos; // per node: first cell, link word, link metric
+    std::vector<uint32_t> rows, cols, metric, best, lmet;
+    std::vector<uint64_t> links;
+  };
+  auto gather = [&](const AllNodesRouteTable& t, const std::vector<std::vector<uint32_t>>& want,
+                    bool older) {
+    Cells c;
+    c.off.assign((size_t)V + 1, 0);
+    c.lwPos.assign((size_t)V + 1, 0);
+    c.lmPos.assign((size_t)V + 1, 0);
+    for (uint32_t i = 0; i < V; ++i) {
+      const uint64_t n = want[i].size();
+      const uint32_t r = older ? rowOf_[i] : i;
+      const uint64_t deg = n ? degOf(t, r) : 0;
+      c.off[i + 1] = c.off[i] + n;
+      c.lwPos[i + 1] = c.lwPos[i] + n * ((deg + 63) / 64);
+      c.lmPos[i + 1] = c.lmPos[i] + (lfa_ ? n * deg : 0);
+      c.rows.insert(c.rows.end(), n, r);
+      c.cols.insert(c.cols.end(), want[i].begin(), want[i].end());
+    }
+    const uint64_t n = c.rows.size();
+    c.metric.resize(n);
+    c.best.resize(n);
+    c.links.resize(c.lwPos[V]);
+    c.lmet.resize(c.lmPos[V]);
+    if (int s = spf_route_table_fetch_cells(
+            t.table_, n, c.rows.data(), c.cols.data(), c.metric.data(), c.best.data(),
+            c.links.data(), lfa_ ? c.lmet.data() : nullptr);
+        s != SPF_OK) {
+      tableFailure("spf_route_table_fetch_cells", s);
+    }
+    return c;
+  };
+  const Cells cn = gather(*this, colsN, false);
+  const Cells co = gather(*older_, colsO, true);
+  const auto t3 = Clock::now();
+
+  // a sparse Row over cells [k0, k1) of one node in a cell list
+  auto view = [&](const AllNodesRouteTable& t, uint32_t r, const uint32_t* cols,
+                  const uint32_t* metric, const uint32_t* best, size_t n, const uint64_t* links,
+                  const uint32_t* lmet) {
+    Row v;
+    v.sparse = true;
+    v.deg = degOf(t, r);
+    v.W = (v.deg + 63) / 64;
+    v.cols.assign(cols, cols + n);
+    v.metric.assign(metric, metric + n);
+    v.best.assign(best, best + n);
+    v.links.assign(links, links + n * v.W);
+    if (lfa_) {
+      v.lmet.assign(lmet, lmet + n * v.deg);
+    }
+    return v;
+  };
+
+  // ---- assembly, node by node on the worker pool
+  parallelFor(V, threads, [&](size_t n, unsigned) {
+    const uint32_t i = (uint32_t)n;
+    DecisionRouteUpdate& u = out[i];
+    const uint32_t ia = rowOf_[i];
+    const bool hasOld = ia != SPF_MAP_NONE;
+    for (uint64_t k = goneOff[i]; k < goneOff[i + 1]; ++k) {
+      const uint32_t c = goneCols_[gone[k]];
+      if (c < Pa) {
+        u.unicastRoutesToDelete.push_back(older_->prefixes_[c]);
+      }
+    }
+    const uint64_t k0 = cellOff[i], k1 = cellOff[i + 1];
+    if (k1 > k0) {
+      const Row r = view(*this, i, col.data() + k0, metric.data() + k0, best.data() + k0,
+                         (size_t)(k1 - k0), links.data() + lwBase[i], lmet.data() + lmBase[i]);
+      for (uint64_t k = k0; k < k1; ++k) {
+        const size_t p = col[k];
+        if (p >= P) {
+          continue; // a label column: among the candidates above
+        }
+        if (metric[k] == 0xFFFFFFFFu) {
+          u.unicastRoutesToDelete.push_back(prefixes_[p]);
+        } else {
+          u.unicastRoutesToUpdate.push_back(materialise(names_[i], i, r, p));
+        }
+      }
+    }
+    if (labelsOf[i].empty()) {
+      return;
+    }
+    const size_t a0 = cn.off[i], b0 = co.off[i];
+    const Row rn = view(*this, i, cn.cols.data() + a0, cn.metric.data() + a0, cn.best.data() + a0,
+                        (size_t)(cn.off[i + 1] - a0), cn.links.data() + cn.lwPos[i],
+                        cn.lmet.data() + cn.lmPos[i]);
+    Row ro;
+    if (hasOld) {
+      ro = view(*older_, ia, co.cols.data() + b0, co.metric.data() + b0, co.best.data() + b0,
+                (size_t)(co.off[i + 1] - b0), co.links.data() + co.lwPos[i],
+                co.lmet.data() + co.lmPos[i]);
+    }
+    for (const int32_t label : labelsOf[i]) {
+      auto ne = mplsEntry(i, rn, label);
+      auto oe = hasOld ? older_->mplsEntry(ia, ro, label) : std::nullopt;
+      if (ne && (!oe || !(*oe == *ne))) {
+        u.mplsRoutesToUpdate.push_back(std::move(*ne));
+      } else if (!ne && oe) {
+        u.mplsRoutesToDelete.push_back(label);
+      }
+    }
+  });
+  const auto t4 = Clock::now();
+
+  st.packUs = us(t0, t1);
+  st.fetchUs = us(t1, t2);
+  st.gatherUs = us(t2, t3);
+  st.assembleUs = us(t3, t4);
+  st.totalUs = us(t0, t4);
+  st.cells = z.cells;
+  st.gone = z.gone;
+  st.linkWords = z.link_words;
+  st.linkMetrics = z.link_metrics;
+  st.newerCells = cn.rows.size();
+  st.olderCells = co.rows.size();
+  // what crossed from the device: the pack's totals, the packed list, and per
+  // gathered cell its metric and best, plus the link words and link metrics
+  st.bytes = 32 + 2 * ((uint64_t)V + 1) * 8 + z.cells * 12 + z.link_words * 8 +
+      z.link_metrics * 4 + z.gone * 4 + (st.newerCells + st.olderCells) * 8 +
+      (cn.links.size() + co.links.size()) * 8 + (cn.lmet.size() + co.lmet.size()) * 4;
+  lastDeltas_ = st;
+  Counters::add("decision.route_table_deltas_us", (int64_t)st.totalUs);
+  Counters::add("decision.route_table_deltas_cells", (int64_t)z.cells);
+  return out;
 }
 
 AllAreasRouteTable::AllAreasRouteTable(

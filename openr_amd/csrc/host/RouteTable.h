@@ -30,9 +30,11 @@
 // built from.
 #pragma once
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <optional>
+#include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
@@ -111,6 +113,28 @@ class AllNodesRouteTable {
   // own label and its adjacency labels in both tables, compared entry by
   // entry against `older` (which must outlive this call).
   DecisionRouteUpdate delta(const std::string& node) const;
+  // delta(nodeName(i)) for every node i of this table, in id order, from ONE
+  // packed fetch instead of two whole rows per node: the changed cells are
+  // compacted on the device (spf_route_table_delta_pack), unicast routes are
+  // materialised straight from them, and the cells MPLS candidates need of
+  // columns that did not change (every column of a candidate label, in both
+  // tables) come from one spf_route_table_fetch_cells per table.  Entry i
+  // holds the updates and deletes of delta(nodeName(i)); the order inside the
+  // four lists is free.  Nodes are assembled on the host worker pool.
+  // `older` must outlive this call.
+  std::vector<DecisionRouteUpdate> deltas() const;
+  // the last deltas(): wall time of its steps, the packed sizes, the cells
+  // gathered from either table and the bytes copied from the device
+  struct DeltasStats {
+    double packUs = 0, fetchUs = 0, gatherUs = 0, assembleUs = 0, totalUs = 0;
+    uint64_t cells = 0, gone = 0, linkWords = 0, linkMetrics = 0;
+    uint64_t newerCells = 0, olderCells = 0, bytes = 0;
+  };
+  const DeltasStats& lastDeltas() const { return lastDeltas_; }
+  // bytes delta(node) copies from the device for a node with a changed cell
+  // and an MPLS candidate (its bitmaps, its whole row and the older table's),
+  // counted from shapes on the host
+  uint64_t deltaFetchBytes(const std::string& node) const;
   // wall time of the device diff call inside the last diff() (maps excluded)
   float diffCallMs() const { return diffCallMs_; }
   // the last diff() went through the maps
@@ -122,14 +146,34 @@ class AllNodesRouteTable {
   size_t numBgpPrefixes() const { return nbgp_; }
 
  private:
+  // The cells of one table row, read through the accessors below: a whole
+  // row (fetchRow), or a sparse view holding only the columns in `cols`
+  // (deltas(): packed changed cells, spf_route_table_fetch_cells lists).
   struct Row {
     std::vector<uint32_t> metric, best;
     std::vector<uint64_t> links;
     std::vector<uint32_t> lmet; // LFA: per-link metrics [cols][deg]
     size_t W = 0, deg = 0;
+    bool sparse = false;
+    std::vector<uint32_t> cols; // sparse: the columns held, ascending
+    // storage index of column p
+    size_t at(size_t p) const {
+      if (!sparse) {
+        return p;
+      }
+      auto it = std::lower_bound(cols.begin(), cols.end(), (uint32_t)p);
+      if (it == cols.end() || *it != p) {
+        throw std::logic_error("AllNodesRouteTable: column not in the sparse row view");
+      }
+      return (size_t)(it - cols.begin());
+    }
+    uint32_t metricOf(size_t p) const { return metric[at(p)]; }
+    uint32_t bestOf(size_t p) const { return best[at(p)]; }
+    const uint64_t* linksOf(size_t p) const { return links.data() + at(p) * W; }
     // metric of link j of cell p (LFA: its own, else the cell's)
     uint32_t linkMetric(size_t p, uint32_t j) const {
-      return lmet.empty() ? metric[p] : lmet[p * deg + j];
+      const size_t s = at(p);
+      return lmet.empty() ? metric[s] : lmet[s * deg + j];
     }
   };
   Row fetchRow(uint32_t i) const;
@@ -185,6 +229,7 @@ class AllNodesRouteTable {
   std::vector<uint32_t> rowOf_;
   std::vector<uint32_t> goneCols_;
   float diffCallMs_{0};
+  mutable DeltasStats lastDeltas_;
   std::vector<uint32_t> diffMapped(const AllNodesRouteTable& older);
   spf_graph* graph_{nullptr};
   spf_query* query_{nullptr};

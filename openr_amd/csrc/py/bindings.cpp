@@ -477,6 +477,82 @@ PYBIND11_MODULE(_openr_spf, m) {
         }
         return py::make_tuple(upd, del);
       })
+      .def("deltas", [](const AllNodesRouteTable& t) {
+        // per node, in id order: (upd, dele, mpls_upd, mpls_dele), rendered
+        // as delta() / delta_mpls() render theirs
+        const std::vector<DecisionRouteUpdate> all = t.deltas();
+        py::list out;
+        for (const DecisionRouteUpdate& u : all) {
+          DecisionRouteDb db;
+          for (const auto& e : u.unicastRoutesToUpdate) {
+            db.unicastEntries.emplace(e.prefix, e);
+          }
+          for (const auto& e : u.mplsRoutesToUpdate) {
+            db.mplsEntries.emplace(e.label, e);
+          }
+          py::dict both = routeDbToPy(db);
+          py::object upd = both["unicast"];
+          py::object mupd = both["mpls"];
+          py::list del, mdel;
+          for (const auto& p : u.unicastRoutesToDelete) {
+            del.append(prefixKey(p));
+          }
+          for (int32_t l : u.mplsRoutesToDelete) {
+            mdel.append(l);
+          }
+          out.append(py::make_tuple(upd, del, mupd, mdel));
+        }
+        return out;
+      })
+      .def("deltas_timed", [](const AllNodesRouteTable& t) {
+        // pack + fetch + gathers + assembly in C++, no Python conversion
+        size_t routes = 0, nodes = 0;
+        {
+          const std::vector<DecisionRouteUpdate> all = t.deltas();
+          for (const DecisionRouteUpdate& u : all) {
+            const size_t n = u.unicastRoutesToUpdate.size() + u.unicastRoutesToDelete.size() +
+                u.mplsRoutesToUpdate.size() + u.mplsRoutesToDelete.size();
+            routes += n;
+            nodes += n != 0;
+          }
+        }
+        const AllNodesRouteTable::DeltasStats& s = t.lastDeltas();
+        py::dict d;
+        d["us"] = s.totalUs;
+        d["pack_us"] = s.packUs;
+        d["fetch_us"] = s.fetchUs;
+        d["gather_us"] = s.gatherUs;
+        d["assemble_us"] = s.assembleUs;
+        d["cells"] = s.cells;
+        d["gone"] = s.gone;
+        d["link_words"] = s.linkWords;
+        d["link_metrics"] = s.linkMetrics;
+        d["newer_cells"] = s.newerCells;
+        d["older_cells"] = s.olderCells;
+        d["bytes"] = s.bytes;
+        d["routes"] = routes;
+        d["nodes"] = nodes;
+        return d;
+      })
+      .def("delta_loop_timed", [](const AllNodesRouteTable& t, const std::vector<std::string>& nodes) {
+        // delta(node) for every listed node in C++, no Python conversion:
+        // (routes in the deltas, wall time in us, bytes copied from the device)
+        size_t routes = 0;
+        uint64_t bytes = 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (const std::string& node : nodes) {
+          const DecisionRouteUpdate u = t.delta(node);
+          routes += u.unicastRoutesToUpdate.size() + u.unicastRoutesToDelete.size() +
+              u.mplsRoutesToUpdate.size() + u.mplsRoutesToDelete.size();
+        }
+        const double us = std::chrono::duration<double, std::micro>(
+                              std::chrono::steady_clock::now() - t0)
+                              .count();
+        for (const std::string& node : nodes) {
+          bytes += t.deltaFetchBytes(node);
+        }
+        return py::make_tuple((long)routes, us, bytes);
+      })
       .def("routes_timed", [](const AllNodesRouteTable& t, const std::string& node) {
         // fetch + materialise the node's routes in C++, no Python conversion
         const auto t0 = std::chrono::steady_clock::now();

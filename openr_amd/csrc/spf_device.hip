@@ -6678,6 +6678,292 @@ __global__ __launch_bounds__(256) void spf_route_table_diff_mapped_kernel(RouteD
   }
 }
 
+// Packed route delta (spf_route_table_delta_pack): the changed cells of the
+// last diff as one record list, i.e. getRouteDelta's (Decision.cpp:47-85)
+// updates and deletes of every node without a whole-row fetch.  A stream
+// compaction over the diff's bitmaps in three steps: count per row, scan over
+// rows, fill.
+//
+// Count: cnt[q] = popcount of row q's changed bitmap, cnt[nq + q] = of its
+// gone bitmap (gone_bits null: 0).  One wave per row.
+__global__ __launch_bounds__(256) void spf_route_delta_count_kernel(
+    const uint64_t* __restrict__ bits, const uint64_t* __restrict__ gone_bits, uint32_t nq,
+    uint32_t pw, uint32_t gw, uint32_t* __restrict__ cnt) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+  const uint32_t nwave = gridDim.x * (blockDim.x / 64);
+  for (uint32_t q = wave; q < nq; q += nwave) {
+    uint32_t n = 0, g = 0;
+    for (uint32_t w = lane; w < pw; w += 64) {
+      n += __popcll(bits[(size_t)q * pw + w]);
+    }
+    for (uint32_t w = lane; gone_bits && w < gw; w += 64) {
+      g += __popcll(gone_bits[(size_t)q * gw + w]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      n += (uint32_t)__shfl_down((int)n, o, 64);
+      g += (uint32_t)__shfl_down((int)g, o, 64);
+    }
+    if (lane == 0) {
+      cnt[q] = n;
+      cnt[nq + q] = g;
+    }
+  }
+}
+
+// block_excl_scan over 64-bit values (the weighted sums of the delta scan:
+// cells x link words and cells x links of a row pass 2^32 on wide tables).
+// `scan` holds kWaves+1 64-bit LDS words.
+template <uint32_t BS>
+__device__ __forceinline__ uint64_t block_excl_scan64(
+    uint64_t x, uint64_t* scan, uint64_t* total) {
+  constexpr uint32_t kWaves = BS / 64;
+  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+  auto up = [](uint64_t v, int o) {
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, o, 64);
+    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), o, 64);
+    return ((uint64_t)hi << 32) | lo;
+  };
+  uint64_t inc = x;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t y = up(inc, o);
+    if (lane >= (uint32_t)o) {
+      inc += y;
+    }
+  }
+  if (lane == 63) {
+    scan[wid] = inc;
+  }
+  __syncthreads();
+  if (wid == 0) {
+    uint64_t w = lane < kWaves ? scan[lane] : 0;
+#pragma unroll
+    for (int o = 1; o < (int)kWaves; o <<= 1) {
+      const uint64_t y = up(w, o);
+      if (lane >= (uint32_t)o) {
+        w += y;
+      }
+    }
+    if (lane < kWaves) {
+      scan[lane] = w;
+    }
+  }
+  __syncthreads();
+  const uint64_t base = wid ? scan[wid - 1] : 0;
+  *total = scan[kWaves - 1];
+  return base + inc - x;
+}
+
+// Scan: exclusive 64-bit offsets over rows of the cell counts, the gone
+// counts and the two weighted sums (cells x link words of the row, cells x
+// links of the row for SPF_RT_LFA).  off = four arrays of nq + 1 (cells,
+// gone, link words, link metrics; entry nq = the total) and the four totals
+// once more behind them, for one small copy to the host.  One workgroup;
+// rows beyond its width take further passes with a running base.
+constexpr uint32_t kDeltaScanBlock = 1024;
+__global__ __launch_bounds__(kDeltaScanBlock) void spf_route_delta_scan_kernel(
+    const uint32_t* __restrict__ cnt, const uint64_t* __restrict__ lk_off,
+    const uint64_t* __restrict__ lm_off, uint32_t P, uint32_t nq, uint64_t* __restrict__ off) {
+  __shared__ uint32_t scan[kDeltaScanBlock / 64 + 1];
+  __shared__ uint64_t scan64[kDeltaScanBlock / 64 + 1];
+  uint64_t* cell_off = off;
+  uint64_t* gone_off = off + ((size_t)nq + 1);
+  uint64_t* lw_off = off + 2 * ((size_t)nq + 1);
+  uint64_t* lmo_off = off + 3 * ((size_t)nq + 1);
+  uint64_t bc = 0, bg = 0, bw = 0, bm = 0;
+  for (uint32_t base = 0; base < nq; base += kDeltaScanBlock) {
+    const uint32_t q = base + threadIdx.x;
+    const bool in = q < nq;
+    const uint32_t c = in ? cnt[q] : 0, g = in ? cnt[nq + q] : 0;
+    const uint64_t W = in && P ? (lk_off[q + 1] - lk_off[q]) / P : 0;
+    const uint64_t deg = in && P && lm_off ? (lm_off[q + 1] - lm_off[q]) / P : 0;
+    uint32_t tc, tg;
+    uint64_t tw, tm;
+    const uint32_t oc = block_excl_scan<kDeltaScanBlock>(c, scan, &tc);
+    __syncthreads();
+    const uint32_t og = block_excl_scan<kDeltaScanBlock>(g, scan, &tg);
+    __syncthreads();
+    const uint64_t ow = block_excl_scan64<kDeltaScanBlock>(c * W, scan64, &tw);
+    __syncthreads();
+    const uint64_t om = block_excl_scan64<kDeltaScanBlock>(c * deg, scan64, &tm);
+    __syncthreads();
+    if (in) {
+      cell_off[q] = bc + oc;
+      gone_off[q] = bg + og;
+      lw_off[q] = bw + ow;
+      lmo_off[q] = bm + om;
+    }
+    bc += tc;
+    bg += tg;
+    bw += tw;
+    bm += tm;
+  }
+  if (threadIdx.x == 0) {
+    cell_off[nq] = bc;
+    gone_off[nq] = bg;
+    lw_off[nq] = bw;
+    lmo_off[nq] = bm;
+    uint64_t* tot = off + 4 * ((size_t)nq + 1);
+    tot[0] = bc;
+    tot[1] = bg;
+    tot[2] = bw;
+    tot[3] = bm;
+  }
+}
+
+// Fill: one workgroup per row, one wave per bitmap word (the shape of
+// spf_route_table_diff_kernel), lane l owns bit l.  The rank of a set bit in
+// its row = set bits of the preceding words (a block scan over word
+// popcounts, kDeltaFillBlock words per pass, with a running prefix over
+// passes) + set bits of its own word below it.  Slots are in cell order, so
+// the lanes of a wave store contiguous runs.
+constexpr uint32_t kDeltaFillBlock = 256;
+struct RouteDeltaFillArgs {
+  const uint64_t* bits;      // [nq * pw]
+  const uint64_t* gone_bits; // [nq * gw] or null
+  const uint32_t* cnt;       // [2 * nq]
+  const uint64_t* off;       // the scan's four offset arrays
+  const uint32_t *metric, *best;
+  const uint64_t *links, *lk_off;
+  const uint32_t* lmet; // null: not LFA
+  const uint64_t* lm_off;
+  uint32_t P, nq, pw, gw;
+  uint32_t *col_out, *metric_out, *best_out, *lmet_out, *gone_out;
+  uint64_t* links_out;
+};
+
+// fn(w, word, rank0) for every non-zero word w of the bitmap row `row`, wave
+// by wave (uniform within a wave); rank0 = set bits of the row before word w.
+template <class Fn>
+__device__ __forceinline__ void delta_ranked_words(
+    const uint64_t* __restrict__ row, uint32_t nw, uint32_t* s_off, uint32_t* scan, Fn&& fn) {
+  constexpr uint32_t kWavesPerBlock = kDeltaFillBlock / 64;
+  const uint32_t wv = threadIdx.x >> 6;
+  uint32_t run = 0;
+  for (uint32_t c0 = 0; c0 < nw; c0 += kDeltaFillBlock) {
+    const uint32_t mine = c0 + threadIdx.x;
+    const uint32_t pc = mine < nw ? (uint32_t)__popcll(row[mine]) : 0;
+    uint32_t total;
+    s_off[threadIdx.x] = block_excl_scan<kDeltaFillBlock>(pc, scan, &total);
+    __syncthreads();
+    const uint32_t n = min(kDeltaFillBlock, nw - c0);
+    for (uint32_t wi = wv; wi < n; wi += kWavesPerBlock) {
+      const uint64_t word = row[c0 + wi];
+      if (word) {
+        fn(c0 + wi, word, run + s_off[wi]);
+      }
+    }
+    run += total;
+    __syncthreads(); // s_off and scan are rewritten by the next pass
+  }
+}
+
+__global__ __launch_bounds__(kDeltaFillBlock) void spf_route_delta_fill_kernel(
+    RouteDeltaFillArgs a) {
+  __shared__ uint32_t s_off[kDeltaFillBlock];
+  __shared__ uint32_t scan[kDeltaFillBlock / 64 + 1];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t P = a.P, nq = a.nq;
+  const uint64_t* cell_off = a.off;
+  const uint64_t* gone_off = a.off + ((size_t)nq + 1);
+  const uint64_t* lw_off = a.off + 2 * ((size_t)nq + 1);
+  const uint64_t* lmo_off = a.off + 3 * ((size_t)nq + 1);
+  for (uint32_t q = blockIdx.x; q < nq; q += gridDim.x) {
+    if (a.cnt[q]) { // uniform over the workgroup
+      const uint32_t W = (uint32_t)((a.lk_off[q + 1] - a.lk_off[q]) / P);
+      const uint32_t deg = a.lmet ? (uint32_t)((a.lm_off[q + 1] - a.lm_off[q]) / P) : 0;
+      const uint64_t* l_q = a.links + a.lk_off[q];
+      const uint32_t* lm_q = a.lmet ? a.lmet + a.lm_off[q] : nullptr;
+      const uint64_t k0 = cell_off[q], lw0 = lw_off[q], lm0 = lmo_off[q];
+      delta_ranked_words(
+          a.bits + (size_t)q * a.pw, a.pw, s_off, scan,
+          [&](uint32_t w, uint64_t word, uint32_t rank0) {
+            const uint32_t below = (uint32_t)__popcll(word & ((1ull << lane) - 1ull));
+            if ((word >> lane) & 1ull) {
+              const uint32_t p = w * 64 + lane; // < P: the diff sets no bit beyond it
+              const uint64_t r = (uint64_t)rank0 + below;
+              const size_t o = (size_t)q * P + p;
+              a.col_out[k0 + r] = p;
+              a.metric_out[k0 + r] = a.metric[o];
+              a.best_out[k0 + r] = a.best[o];
+              for (uint32_t j = 0; j < W; ++j) {
+                a.links_out[lw0 + r * W + j] = l_q[(size_t)p * W + j];
+              }
+            }
+            if (lm_q) { // the wave copies each cell's deg link metrics together
+              uint64_t m = word;
+              uint32_t r = rank0;
+              while (m) {
+                const uint32_t p = w * 64 + (uint32_t)__builtin_ctzll(m);
+                m &= m - 1;
+                for (uint32_t j = lane; j < deg; j += 64) {
+                  a.lmet_out[lm0 + (uint64_t)r * deg + j] = lm_q[(size_t)p * deg + j];
+                }
+                ++r;
+              }
+            }
+          });
+    }
+    if (a.gone_bits && a.cnt[nq + q]) {
+      const uint64_t g0 = gone_off[q];
+      delta_ranked_words(
+          a.gone_bits + (size_t)q * a.gw, a.gw, s_off, scan,
+          [&](uint32_t w, uint64_t word, uint32_t rank0) {
+            if ((word >> lane) & 1ull) {
+              a.gone_out[g0 + rank0 + (uint32_t)__popcll(word & ((1ull << lane) - 1ull))] =
+                  w * 64 + lane;
+            }
+          });
+    }
+  }
+}
+
+// Sparse read of a route table (spf_route_table_fetch_cells): cell k =
+// (rows[k], cols[k]); one lane per cell copies metric, best and the row's
+// link words to pos[k] (the host's running sum of link words).
+__global__ __launch_bounds__(256) void spf_route_cells_gather_kernel(
+    const uint32_t* __restrict__ rows, const uint32_t* __restrict__ cols,
+    const uint64_t* __restrict__ pos, uint64_t n, uint32_t P,
+    const uint32_t* __restrict__ metric, const uint32_t* __restrict__ best,
+    const uint64_t* __restrict__ links, const uint64_t* __restrict__ lk_off,
+    uint32_t* __restrict__ metric_out, uint32_t* __restrict__ best_out,
+    uint64_t* __restrict__ links_out) {
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n;
+       k += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t q = rows[k], p = cols[k];
+    const size_t o = (size_t)q * P + p;
+    metric_out[k] = metric[o];
+    best_out[k] = best[o];
+    const uint32_t W = (uint32_t)((lk_off[q + 1] - lk_off[q]) / P);
+    const uint64_t* src = links + lk_off[q] + (size_t)p * W;
+    for (uint32_t j = 0; j < W; ++j) {
+      links_out[pos[k] + j] = src[j];
+    }
+  }
+}
+
+// The SPF_RT_LFA link metrics of the listed cells: one wave per cell, deg
+// metrics to pos[k] (the host's running sum of row degrees).
+__global__ __launch_bounds__(256) void spf_route_cells_gather_lmet_kernel(
+    const uint32_t* __restrict__ rows, const uint32_t* __restrict__ cols,
+    const uint64_t* __restrict__ pos, uint64_t n, uint32_t P,
+    const uint32_t* __restrict__ lmet, const uint64_t* __restrict__ lm_off,
+    uint32_t* __restrict__ lmet_out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t nwave = (uint64_t)gridDim.x * (blockDim.x / 64);
+  for (uint64_t k = (uint64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); k < n;
+       k += nwave) {
+    const uint32_t q = rows[k], p = cols[k];
+    const uint32_t deg = (uint32_t)((lm_off[q + 1] - lm_off[q]) / P);
+    const uint32_t* src = lmet + lm_off[q] + (size_t)p * deg;
+    for (uint32_t j = lane; j < deg; j += 64) {
+      lmet_out[pos[k] + j] = src[j];
+    }
+  }
+}
+
 // ------------------------------------------------ k-th path traces (KSP2)
 //
 // getKthPaths' trace loop (LinkState.cpp:776-786) over one query row: repeated
@@ -14111,6 +14397,18 @@ struct spf_route_table {
   size_t gone_cap = 0; // uint64 words
   uint32_t gone_n = 0;
   bool mapped = false;
+  // spf_route_table_delta_pack / _fetch_cells: `epoch` counts runs and diffs
+  // (a pack is stale once it moved on); the packed list and the gather
+  // staging are grow-only buffers (capacities in elements)
+  uint64_t epoch = 0, pk_epoch = 0;
+  bool diffed = false, diff_mapped_last = false, packed = false;
+  spf_route_delta_sizes pk{};
+  uint32_t *d_pk_cnt = nullptr, *d_pk_cell = nullptr, *d_pk_lmet = nullptr, *d_pk_gone = nullptr;
+  uint64_t *d_pk_off = nullptr, *d_pk_links = nullptr;
+  size_t pk_cell_cap = 0, pk_lmet_cap = 0, pk_gone_cap = 0, pk_links_cap = 0;
+  uint32_t *d_gc_idx = nullptr, *d_gc_out = nullptr, *d_gc_lmet = nullptr;
+  uint64_t *d_gc_pos = nullptr, *d_gc_links = nullptr;
+  size_t gc_idx_cap = 0, gc_out_cap = 0, gc_lmet_cap = 0, gc_pos_cap = 0, gc_links_cap = 0;
 };
 
 namespace {
@@ -14123,7 +14421,10 @@ void free_route_table(spf_route_table* t) {
   for (void* p : {(void*)t->d_ann_off, (void*)t->d_ann, (void*)t->d_metric, (void*)t->d_best,
                   (void*)t->d_lk_off, (void*)t->d_links, (void*)t->d_diff, (void*)t->d_count,
                   (void*)t->d_lm_off, (void*)t->d_lmet, (void*)t->d_row_of, (void*)t->d_map,
-                  (void*)t->d_gone}) {
+                  (void*)t->d_gone, (void*)t->d_pk_cnt, (void*)t->d_pk_cell, (void*)t->d_pk_lmet,
+                  (void*)t->d_pk_gone, (void*)t->d_pk_off, (void*)t->d_pk_links,
+                  (void*)t->d_gc_idx, (void*)t->d_gc_out, (void*)t->d_gc_lmet, (void*)t->d_gc_pos,
+                  (void*)t->d_gc_links}) {
     if (p) {
       (void)hipFree(p);
     }
@@ -14308,6 +14609,8 @@ int spf_route_table_run(spf_route_table* t) {
   }
   HIP_TRY(hipEventRecord(t->ev1, g->stream));
   t->ran = true;
+  ++t->epoch; // the bitmaps of an earlier diff describe the rows just overwritten
+  t->diffed = false;
   return SPF_OK;
 }
 
@@ -14401,6 +14704,9 @@ int spf_route_table_diff(spf_route_table* older, spf_route_table* newer, uint32_
                 "tables differ in rows, prefixes or link layout (rematerialise instead)");
   }
   const uint32_t nq = newer->q->nq, P = newer->P, pw = (P + 63) / 64;
+  ++newer->epoch;
+  newer->diffed = true;
+  newer->diff_mapped_last = false;
   if (nq == 0) {
     return SPF_OK;
   }
@@ -14581,6 +14887,9 @@ int spf_route_table_diff_mapped(
   }
   newer->gone_n = ng;
   newer->mapped = true;
+  ++newer->epoch;
+  newer->diffed = true;
+  newer->diff_mapped_last = true;
   if (nq == 0) {
     return SPF_OK;
   }
@@ -14693,6 +15002,224 @@ int spf_route_table_changed_gone(spf_route_table* t, uint32_t i, uint64_t* bits)
   HIP_TRY(hipSetDevice(t->q->g->device));
   HIP_TRY(hipStreamSynchronize(t->q->g->stream));
   HIP_TRY(hipMemcpy(bits, t->d_gone + (size_t)i * gw, (size_t)gw * 8, hipMemcpyDeviceToHost));
+  return SPF_OK;
+}
+
+} // extern "C"
+
+namespace {
+// grow-only device buffer of `n` elements (contents are not kept)
+template <class T>
+int grow_dev(T** p, size_t* cap, size_t n) {
+  if (n <= *cap) {
+    return SPF_OK;
+  }
+  if (*p) {
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+  }
+  if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess) {
+    return fail(SPF_E_NOMEM, "route delta buffer");
+  }
+  *cap = n;
+  return SPF_OK;
+}
+} // namespace
+
+extern "C" {
+
+int spf_route_table_delta_pack(spf_route_table* t, spf_route_delta_sizes* sizes) {
+  SPF_ABI_RANGE("spf_route_table_delta_pack");
+  if (!t || !sizes) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  *sizes = spf_route_delta_sizes{};
+  if (!t->ran || !t->diffed) {
+    return fail(SPF_E_INVALID, "no diff has run on this table since its last run");
+  }
+  t->packed = false;
+  spf_graph* g = t->q->g;
+  const uint32_t nq = t->q->nq, P = t->P, pw = (P + 63) / 64;
+  const uint32_t gw = t->diff_mapped_last ? (t->gone_n + 63) / 64 : 0;
+  t->pk = spf_route_delta_sizes{};
+  if (nq && (pw || gw)) {
+    HIP_TRY(hipSetDevice(g->device));
+    if (!t->d_pk_cnt) {
+      HIP_TRY(hipMalloc((void**)&t->d_pk_cnt, (size_t)nq * 2 * 4));
+      HIP_TRY(hipMalloc((void**)&t->d_pk_off, (4 * ((size_t)nq + 1) + 4) * 8));
+    }
+    const uint64_t* gone_bits = gw ? t->d_gone : nullptr;
+    const uint32_t waves = 256 / 64;
+    const uint32_t cgrid =
+        std::min<uint32_t>((nq + waves - 1) / waves, (uint32_t)g->num_cus * 8);
+    SPF_LAUNCH(spf_route_delta_count_kernel, dim3(cgrid), dim3(256), 0, g->stream, t->d_diff,
+               gone_bits, nq, pw, gw, t->d_pk_cnt);
+    HIP_TRY(hipGetLastError());
+    SPF_LAUNCH(spf_route_delta_scan_kernel, dim3(1), dim3(kDeltaScanBlock), 0, g->stream,
+               t->d_pk_cnt, t->d_lk_off, t->lfa ? t->d_lm_off : nullptr, P, nq, t->d_pk_off);
+    HIP_TRY(hipGetLastError());
+    uint64_t tot[4];
+    HIP_TRY(hipMemcpyAsync(tot, t->d_pk_off + 4 * ((size_t)nq + 1), sizeof(tot),
+                           hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream)); // the totals size the output
+    t->pk.cells = tot[0];
+    t->pk.gone = tot[1];
+    t->pk.link_words = tot[2];
+    t->pk.link_metrics = t->lfa ? tot[3] : 0;
+    if (t->pk.cells || t->pk.gone) {
+      int st = SPF_OK;
+      if ((st = grow_dev(&t->d_pk_cell, &t->pk_cell_cap, (size_t)t->pk.cells * 3)) ||
+          (st = grow_dev(&t->d_pk_links, &t->pk_links_cap, (size_t)t->pk.link_words)) ||
+          (st = grow_dev(&t->d_pk_lmet, &t->pk_lmet_cap, (size_t)t->pk.link_metrics)) ||
+          (st = grow_dev(&t->d_pk_gone, &t->pk_gone_cap, (size_t)t->pk.gone))) {
+        return st;
+      }
+      RouteDeltaFillArgs a{};
+      a.bits = t->d_diff;
+      a.gone_bits = gone_bits;
+      a.cnt = t->d_pk_cnt;
+      a.off = t->d_pk_off;
+      a.metric = t->d_metric;
+      a.best = t->d_best;
+      a.links = t->d_links;
+      a.lk_off = t->d_lk_off;
+      a.lmet = t->lfa ? t->d_lmet : nullptr;
+      a.lm_off = t->d_lm_off;
+      a.P = P;
+      a.nq = nq;
+      a.pw = pw;
+      a.gw = gw;
+      a.col_out = t->d_pk_cell;
+      a.metric_out = t->d_pk_cell + t->pk.cells;
+      a.best_out = t->d_pk_cell + 2 * t->pk.cells;
+      a.links_out = t->d_pk_links;
+      a.lmet_out = t->d_pk_lmet;
+      a.gone_out = t->d_pk_gone;
+      const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)g->num_cus * 8);
+      SPF_LAUNCH(spf_route_delta_fill_kernel, dim3(grid), dim3(kDeltaFillBlock), 0, g->stream, a);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  t->packed = true;
+  t->pk_epoch = t->epoch;
+  *sizes = t->pk;
+  return SPF_OK;
+}
+
+int spf_route_table_delta_fetch(
+    spf_route_table* t, uint64_t* cell_off, uint32_t* col, uint32_t* metric, uint32_t* best,
+    uint64_t* links, uint32_t* link_metrics, uint64_t* gone_off, uint32_t* gone) {
+  SPF_ABI_RANGE("spf_route_table_delta_fetch");
+  if (!t || !cell_off || !gone_off) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  if (!t->packed) {
+    return fail(SPF_E_INVALID, "no delta has been packed on this table");
+  }
+  if (t->pk_epoch != t->epoch) {
+    return fail(SPF_E_INVALID, "the packed delta is stale (the table ran or diffed since)");
+  }
+  const spf_route_delta_sizes& z = t->pk;
+  if ((z.cells && (!col || !metric || !best)) || (z.link_words && !links) ||
+      (z.link_metrics && !link_metrics) || (z.gone && !gone)) {
+    return fail(SPF_E_INVALID, "null output for a non-empty list");
+  }
+  const size_t nq = t->q->nq;
+  if (!z.cells && !z.gone) { // nothing was launched; the offset arrays may not exist
+    std::fill(cell_off, cell_off + nq + 1, (uint64_t)0);
+    std::fill(gone_off, gone_off + nq + 1, (uint64_t)0);
+    return SPF_OK;
+  }
+  spf_graph* g = t->q->g;
+  HIP_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  auto get = [](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  HIP_TRY(get(cell_off, t->d_pk_off, (nq + 1) * 8));
+  HIP_TRY(get(gone_off, t->d_pk_off + (nq + 1), (nq + 1) * 8));
+  HIP_TRY(get(col, t->d_pk_cell, z.cells * 4));
+  HIP_TRY(get(metric, t->d_pk_cell + z.cells, z.cells * 4));
+  HIP_TRY(get(best, t->d_pk_cell + 2 * z.cells, z.cells * 4));
+  HIP_TRY(get(links, t->d_pk_links, z.link_words * 8));
+  HIP_TRY(get(link_metrics, t->d_pk_lmet, z.link_metrics * 4));
+  HIP_TRY(get(gone, t->d_pk_gone, z.gone * 4));
+  return SPF_OK;
+}
+
+int spf_route_table_fetch_cells(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* metric,
+    uint32_t* best, uint64_t* links, uint32_t* link_metrics) {
+  SPF_ABI_RANGE("spf_route_table_fetch_cells");
+  if (!t) {
+    return fail(SPF_E_INVALID, "null table");
+  }
+  if (!t->ran) {
+    return fail(SPF_E_INVALID, "table has not run");
+  }
+  if (n == 0) {
+    return SPF_OK;
+  }
+  if (!rows || !cols || !metric || !best) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  // ---- validation (host): every index the kernels follow is in range
+  const uint32_t nq = t->q->nq, P = t->P;
+  std::vector<uint64_t> pos(t->lfa ? 2 * n : n);
+  uint64_t nl = 0, nm = 0;
+  for (uint64_t k = 0; k < n; ++k) {
+    if (rows[k] >= nq || cols[k] >= P) {
+      return fail(SPF_E_INVALID, "cell row or column out of range");
+    }
+    pos[k] = nl;
+    nl += (t->lk_off[rows[k] + 1] - t->lk_off[rows[k]]) / P;
+    if (t->lfa) {
+      pos[n + k] = nm;
+      nm += t->deg[rows[k]];
+    }
+  }
+  if ((nl && !links) || (nm && !link_metrics)) {
+    return fail(SPF_E_INVALID, "null links or link_metrics");
+  }
+  spf_graph* g = t->q->g;
+  HIP_TRY(hipSetDevice(g->device));
+  int st = SPF_OK;
+  if ((st = grow_dev(&t->d_gc_idx, &t->gc_idx_cap, (size_t)n * 2)) ||
+      (st = grow_dev(&t->d_gc_pos, &t->gc_pos_cap, pos.size())) ||
+      (st = grow_dev(&t->d_gc_out, &t->gc_out_cap, (size_t)n * 2)) ||
+      (st = grow_dev(&t->d_gc_links, &t->gc_links_cap, (size_t)nl)) ||
+      (st = grow_dev(&t->d_gc_lmet, &t->gc_lmet_cap, (size_t)nm))) {
+    return st;
+  }
+  // the staging buffers are reused by the next call: every copy below has
+  // landed (stream order, then the final synchronise) before this one returns
+  HIP_TRY(hipMemcpyAsync(t->d_gc_idx, rows, n * 4, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemcpyAsync(t->d_gc_idx + n, cols, n * 4, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemcpyAsync(t->d_gc_pos, pos.data(), pos.size() * 8, hipMemcpyHostToDevice,
+                         g->stream));
+  const uint32_t maxGrid = (uint32_t)g->num_cus * 8;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, maxGrid);
+  SPF_LAUNCH(spf_route_cells_gather_kernel, dim3(grid), dim3(256), 0, g->stream, t->d_gc_idx,
+             t->d_gc_idx + n, t->d_gc_pos, n, P, t->d_metric, t->d_best, t->d_links, t->d_lk_off,
+             t->d_gc_out, t->d_gc_out + n, t->d_gc_links);
+  HIP_TRY(hipGetLastError());
+  if (nm) {
+    const uint32_t wgrid = (uint32_t)std::min<uint64_t>((n + 3) / 4, maxGrid);
+    SPF_LAUNCH(spf_route_cells_gather_lmet_kernel, dim3(wgrid), dim3(256), 0, g->stream,
+               t->d_gc_idx, t->d_gc_idx + n, t->d_gc_pos + n, n, P, t->d_lmet, t->d_lm_off,
+               t->d_gc_lmet);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipMemcpyAsync(metric, t->d_gc_out, n * 4, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipMemcpyAsync(best, t->d_gc_out + n, n * 4, hipMemcpyDeviceToHost, g->stream));
+  if (nl) {
+    HIP_TRY(hipMemcpyAsync(links, t->d_gc_links, nl * 8, hipMemcpyDeviceToHost, g->stream));
+  }
+  if (nm) {
+    HIP_TRY(hipMemcpyAsync(link_metrics, t->d_gc_lmet, nm * 4, hipMemcpyDeviceToHost, g->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(g->stream));
   return SPF_OK;
 }
 
