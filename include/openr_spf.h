@@ -441,6 +441,61 @@ int spf_route_table_fetch(
  * j of the cell's link mask is; the diff compares these too. */
 int spf_route_table_fetch_link_metrics(spf_route_table* t, uint32_t i, uint32_t* out);
 
+/* ---- selected columns: BGP best path per node with the IGP cost ----
+ * With bgpUseIgpMetric the metric-vector selection (SpfSolverImpl::
+ * runBestPathSelectionBgp, Decision.cpp:714-803) differs per node: every
+ * candidate's vector gets an OPENR_IGP_COST entity holding -d(node,
+ * announcer) before the fold (:746-766).  compareMetricVectors(mv_i + igp_i,
+ * mv_b + igp_b) depends on the two IGP values only through the sign of
+ * d_i - d_b, so the caller gives three CompareResult codes per ordered pair
+ * and spf_route_select_kernel folds every (row, selected column) on the
+ * device, in the order of the column's announcers[] ("candidates"):
+ * unreachable candidates are skipped (:726-733), the first reachable one is
+ * a WINNER, igp = min d over every reachable candidate (bestIgpMetric),
+ * TIE / ERROR end the fold with no route (:784-792).  Then
+ * maybeFilterDrainedNodes (:651-666) on the winners through the graph's
+ * node_overloaded bits, and selectEcmpBgp's (:805-866) refusals: no winner,
+ * the row's node among the filtered winners, or a best candidate without
+ * loopback.  The route kernel then computes the cell as for any column, over
+ * the candidates in the winners word only, with `best` = the fold's best
+ * candidate (not re-chosen by the drain filter). */
+typedef struct spf_route_select_desc {
+  uint32_t num_selected;
+  const uint32_t* columns;      /* [num_selected] distinct column indices, each with at most
+                                   32 announcers */
+  const uint64_t* pair_offsets; /* [num_selected + 1]: column k's pair table is pair_codes[
+                                   pair_offsets[k] ..), at least n(n-1)/2 entries */
+  const uint16_t* pair_codes;   /* entry i(i-1)/2 + b (b < i, candidate indices): candidate i
+                                   against a current best b; bits 0-2 the result when i is
+                                   closer than b, 3-5 at equal distance, 6-8 when farther.
+                                   Codes: 0 WINNER, 1 TIE_WINNER, 2 TIE, 3 TIE_LOOSER,
+                                   4 LOOSER, 5 ERROR (6, 7 read as ERROR) */
+  const uint8_t* cand_flags;    /* parallel to announcers[] (entries of unselected columns
+                                   are ignored): bit 0 = the candidate has exactly one
+                                   loopback via of the prefix family
+                                   (PrefixState::getLoopbackVias, PrefixState.cpp:111-126) */
+} spf_route_select_desc;
+/* spf_route_table_create_ex with selected columns (sel NULL or empty: the
+ * same table as create_ex builds, run by the same kernel instance). */
+int spf_route_table_create_sel(
+    spf_query* q, uint32_t num_prefixes, const uint32_t* ann_offsets,
+    const uint32_t* announcers, uint32_t flags, const spf_route_select_desc* sel,
+    spf_route_table** out);
+/* Device time of spf_route_select_kernel in the last run (0 without selected
+ * columns); spf_route_table_elapsed_ms stays the route kernel's alone. */
+int spf_route_table_select_elapsed_ms(spf_route_table* t, float* ms);
+/* spf_route_table_fetch plus, per column, the selection's words: igp[P]
+ * (bestIgpMetric, Decision.cpp:752-755: the bestNexthop metric of
+ * selectEcmpBgp :829-831) and winners[P] (bit c = candidate c of the column
+ * is a next-hop destination).  Unselected columns and cells without a route
+ * read igp UINT32_MAX, winners 0; in a selected column `best` is the fold's
+ * best candidate.  spf_route_table_diff and _diff_mapped compare metric,
+ * best and links as for any column and ignore the igp word (the host layer's
+ * AllNodesRouteTable::diff refuses tables with BGP columns altogether). */
+int spf_route_table_fetch_sel(
+    spf_route_table* t, uint32_t i, uint32_t* metric, uint32_t* best, uint64_t* links,
+    uint32_t* igp, uint32_t* winners);
+
 /* Network-wide route delta: compare two tables built
  * over graphs with the same CSR layout (e.g. before and after an overload or
  * metric change) and the same prefixes; cell (i, p) changed iff its metric,

@@ -69,6 +69,9 @@ EXPORTED_SYMBOLS = (
     "spf_route_table_create_ex",
     "spf_table_nexthops",
     "spf_route_table_fetch_link_metrics",
+    "spf_route_table_create_sel",
+    "spf_route_table_select_elapsed_ms",
+    "spf_route_table_fetch_sel",
     "spf_query_device_rows",
     "spf_query_row_stride",
     "spf_query_fetch_rows",
@@ -247,6 +250,16 @@ class _RouteDiffMap(C.Structure):
     ]
 
 
+class _RouteSelectDesc(C.Structure):
+    _fields_ = [
+        ("num_selected", C.c_uint32),
+        ("columns", C.POINTER(C.c_uint32)),
+        ("pair_offsets", C.POINTER(C.c_uint64)),
+        ("pair_codes", C.POINTER(C.c_uint16)),
+        ("cand_flags", C.POINTER(C.c_uint8)),
+    ]
+
+
 class _RouteDeltaSizes(C.Structure):
     _fields_ = [
         ("cells", C.c_uint64),
@@ -389,6 +402,10 @@ def load():
         "spf_table_levels_buffer": (C.c_int, [vp, u32, C.POINTER(vp), pu64, pu64]),
         "spf_route_table_create": (C.c_int, [vp, u32, pu32, pu32, C.POINTER(vp)]),
         "spf_route_table_create_ex": (C.c_int, [vp, u32, pu32, pu32, u32, C.POINTER(vp)]),
+        "spf_route_table_create_sel": (C.c_int, [vp, u32, pu32, pu32, u32,
+                                                 C.POINTER(_RouteSelectDesc), C.POINTER(vp)]),
+        "spf_route_table_select_elapsed_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "spf_route_table_fetch_sel": (C.c_int, [vp, u32, pu32, pu32, pu64, pu32, pu32]),
         "spf_route_table_destroy": (C.c_int, [vp]),
         "spf_route_table_run": (C.c_int, [vp]),
         "spf_route_table_elapsed_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
@@ -925,9 +942,11 @@ class Query:
 
 class RouteTable:
     """All-nodes route table over a run Query (spf_route_table_*): prefix p
-    is announced by announcers[p] (node ids)."""
+    is announced by announcers[p] (node ids).  selected (optional): {column:
+    (pair_codes, cand_flags)} -- the column's spf_route_select_desc pair table
+    (n(n-1)/2 packed entries) and per-candidate flags (spf_route_table_create_sel)."""
 
-    def __init__(self, query: Query, announcers, flags=0):
+    def __init__(self, query: Query, announcers, flags=0, selected=None):
         lib = load()
         self.query = query
         self.P = len(announcers)
@@ -936,9 +955,29 @@ class RouteTable:
         flat = [int(x) for a in announcers for x in a]
         ann = np.asarray(flat if flat else [0], dtype=np.uint32)
         h = C.c_void_p()
-        _check(lib.spf_route_table_create_ex(query.h, self.P, _p(off, C.c_uint32),
-                                             _p(ann, C.c_uint32), flags, C.byref(h)),
-               "spf_route_table_create_ex")
+        if selected is None:
+            _check(lib.spf_route_table_create_ex(query.h, self.P, _p(off, C.c_uint32),
+                                                 _p(ann, C.c_uint32), flags, C.byref(h)),
+                   "spf_route_table_create_ex")
+        else:
+            cols = np.asarray(sorted(selected), dtype=np.uint32)
+            poff = np.zeros(len(cols) + 1, dtype=np.uint64)
+            codes, cflags = [], np.zeros(max(len(flat), 1), dtype=np.uint8)
+            for k, c in enumerate(cols):
+                pc, cf = selected[int(c)]
+                codes.extend(int(x) for x in pc)
+                poff[k + 1] = len(codes)
+                if int(c) < self.P:  # (an out-of-range column is the library's to refuse)
+                    n = min(len(cf), int(off[c + 1] - off[c]))
+                    cflags[off[c]:off[c] + n] = cf[:n]
+            pcs = np.asarray(codes if codes else [0], dtype=np.uint16)
+            cols_arr = cols if len(cols) else np.zeros(1, dtype=np.uint32)
+            d = _RouteSelectDesc(len(cols), _p(cols_arr, C.c_uint32), _p(poff, C.c_uint64),
+                                 _p(pcs, C.c_uint16), _p(cflags, C.c_uint8))
+            _check(lib.spf_route_table_create_sel(query.h, self.P, _p(off, C.c_uint32),
+                                                  _p(ann, C.c_uint32), flags, C.byref(d),
+                                                  C.byref(h)),
+                   "spf_route_table_create_sel")
         self.h = h
         self.n = query.n
         self.lfa = bool(flags & SPF_RT_LFA)
@@ -971,6 +1010,26 @@ class RouteTable:
         _check(load().spf_route_table_fetch(self.h, i, _p(metric, C.c_uint32), _p(best, C.c_uint32),
                                             _p(links, C.c_uint64)), "spf_route_table_fetch")
         return metric[: self.P], best[: self.P], links[: self.P * W].reshape(self.P, W)
+
+    def fetch_sel(self, i: int):
+        """spf_route_table_fetch_sel: fetch(i) plus (igp [P], winners [P])."""
+        W = self.link_words(i)
+        metric = np.zeros(max(self.P, 1), dtype=np.uint32)
+        best = np.zeros(max(self.P, 1), dtype=np.uint32)
+        links = np.zeros(max(self.P * W, 1), dtype=np.uint64)
+        igp = np.zeros(max(self.P, 1), dtype=np.uint32)
+        winners = np.zeros(max(self.P, 1), dtype=np.uint32)
+        _check(load().spf_route_table_fetch_sel(
+            self.h, i, _p(metric, C.c_uint32), _p(best, C.c_uint32), _p(links, C.c_uint64),
+            _p(igp, C.c_uint32), _p(winners, C.c_uint32)), "spf_route_table_fetch_sel")
+        return (metric[: self.P], best[: self.P], links[: self.P * W].reshape(self.P, W),
+                igp[: self.P], winners[: self.P])
+
+    def select_ms(self) -> float:
+        ms = C.c_float()
+        _check(load().spf_route_table_select_elapsed_ms(self.h, C.byref(ms)),
+               "spf_route_table_select_elapsed_ms")
+        return ms.value
 
     def fetch_link_metrics(self, i: int, deg: int) -> np.ndarray:
         """SPF_RT_LFA: per-link metrics of row i, [P, deg]."""

@@ -29,7 +29,8 @@ int64_t usSince(std::chrono::steady_clock::time_point t0) {
 
 AllNodesRouteTable::AllNodesRouteTable(
     const LinkState& ls, const PrefixState& ps, bool enableV4, bool computeLfa,
-    const std::unordered_set<std::string>* borderNodes, bool bgpColumns, bool bgpDryRun)
+    const std::unordered_set<std::string>* borderNodes, bool bgpColumns, bool bgpDryRun,
+    bool bgpUseIgpMetric)
     : area_(ls.getArea()), enableV4_(enableV4), lfa_(computeLfa), bgpDryRun_(bgpDryRun) {
   auto tp = std::chrono::steady_clock::now();
   LinkState::Engine& eng = ls.engine();
@@ -105,6 +106,7 @@ AllNodesRouteTable::AllNodesRouteTable(
       std::vector<uint8_t> keep(items.size(), 0);
       std::vector<std::vector<Announcer>> anns(items.size());
       std::vector<std::optional<BgpSel>> sels(items.size());
+      std::vector<std::optional<SelCol>> selCols(items.size());
       // BGP candidates: every in-graph announcer (the selection assumes each
       // is reachable from every node; checked below)
       std::vector<std::vector<uint32_t>> bgpAll(items.size());
@@ -150,9 +152,54 @@ AllNodesRouteTable::AllNodesRouteTable(
         if (otherArea) {
           return; // (interior-node tables of several areas: BGP stays on the host)
         }
+        namespace mvu = MetricVectorUtils;
+        if (bgpUseIgpMetric) {
+          // a selected column: the fold runs per node on the device
+          // (spf_route_select_kernel).  Candidates = in-graph announcers in
+          // fold order, without those that advertise OPENR_IGP_COST
+          // (Decision.cpp:735-744: skipped before bestIgpMetric sees them)
+          SelCol sc;
+          std::vector<const thrift::MetricVector*> mvs;
+          const bool isV4 = prefix.prefixAddress.addr.size() == 4;
+          for (const auto& [node, byArea] : entries) {
+            for (const auto& [area, entry] : byArea) {
+              auto it = ids_.find(node);
+              if (it == ids_.end()) {
+                continue; // not in the graph: unreachable from every node
+              }
+              const thrift::MetricVector& mv = entry.mv.value();
+              if (mvu::getMetricEntityByType(mv, mvu::kOpenrIgpCostType)) {
+                continue;
+              }
+              for (const auto& me : mv.metrics) {
+                if (me.priority == mvu::kOpenrIgpCostPriority) {
+                  return; // std::sort leaves its order against the IGP entity open: host
+                }
+              }
+              anns[i].push_back(Announcer{it->second, entry});
+              mvs.push_back(&mv);
+              auto vias = ps.getLoopbackVias({node}, isV4, std::nullopt);
+              sc.via.push_back(vias.size() == 1 ? std::optional<thrift::NextHopThrift>(vias[0])
+                                                : std::nullopt);
+            }
+          }
+          if (mvs.size() > 32) {
+            anns[i].clear();
+            return; // the winners word has 32 bits: host
+          }
+          for (size_t c = 1; c < mvs.size(); ++c) {
+            for (size_t b = 0; b < c; ++b) {
+              const auto codes = mvu::bgpIgpPairCodes(*mvs[c], *mvs[b]);
+              sc.pair.push_back((uint16_t)((unsigned)codes[0] | ((unsigned)codes[1] << 3) |
+                                           ((unsigned)codes[2] << 6)));
+            }
+          }
+          selCols[i] = std::move(sc);
+          keep[i] = 3;
+          return;
+        }
         // runBestPathSelectionBgp (Decision.cpp:714-803) without the IGP
         // cost, every in-graph announcer reachable: entries in map order
-        namespace mvu = MetricVectorUtils;
         std::optional<thrift::MetricVector> bestVector;
         std::set<std::string> winners;
         std::string bestNode, bestArea;
@@ -252,7 +299,8 @@ AllNodesRouteTable::AllNodesRouteTable(
           prefixes_.push_back(*items[i].first);
           announcers_.push_back(std::move(anns[i]));
           bgp_.push_back(keep[i] == 2 ? std::move(sels[i]) : std::nullopt);
-          nbgp_ += keep[i] == 2;
+          sel_.push_back(std::move(selCols[i]));
+          nbgp_ += keep[i] >= 2;
         }
       }
     }
@@ -271,6 +319,8 @@ AllNodesRouteTable::AllNodesRouteTable(
       std::vector<thrift::IpPrefix> px;
       std::vector<std::vector<Announcer>> ax;
       std::vector<std::optional<BgpSel>> bx;
+      std::vector<std::optional<SelCol>> sx;
+      sx.reserve(order.size());
       px.reserve(order.size());
       ax.reserve(order.size());
       bx.reserve(order.size());
@@ -278,7 +328,9 @@ AllNodesRouteTable::AllNodesRouteTable(
         px.push_back(std::move(prefixes_[i]));
         ax.push_back(std::move(announcers_[i]));
         bx.push_back(std::move(bgp_[i]));
+        sx.push_back(std::move(sel_[i]));
       }
+      sel_ = std::move(sx);
       prefixes_ = std::move(px);
       announcers_ = std::move(ax);
       bgp_ = std::move(bx);
@@ -341,9 +393,33 @@ AllNodesRouteTable::AllNodesRouteTable(
     }, 64);
     Counters::add("decision.route_table_host_us", usSince(tp));
     tp = std::chrono::steady_clock::now();
-    if ((s = spf_route_table_create_ex(
+    // selected columns: pair tables and loopback bits parallel to ann
+    std::vector<uint32_t> selColumns;
+    std::vector<uint64_t> pairOff{0};
+    std::vector<uint16_t> pairCodes;
+    std::vector<uint8_t> candFlags(ann.size(), 0);
+    for (size_t p = 0; p < prefixes_.size(); ++p) {
+      if (!sel_[p]) {
+        continue;
+      }
+      selColumns.push_back((uint32_t)p);
+      pairCodes.insert(pairCodes.end(), sel_[p]->pair.begin(), sel_[p]->pair.end());
+      pairOff.push_back(pairCodes.size());
+      for (size_t c = 0; c < sel_[p]->via.size(); ++c) {
+        candFlags[annOff[p] + c] = sel_[p]->via[c] ? 1 : 0;
+      }
+    }
+    nsel_ = selColumns.size();
+    spf_route_select_desc sd{};
+    sd.num_selected = (uint32_t)selColumns.size();
+    sd.columns = selColumns.data();
+    sd.pair_offsets = pairOff.data();
+    sd.pair_codes = pairCodes.data();
+    sd.cand_flags = candFlags.data();
+    if ((s = spf_route_table_create_sel(
              query_, (uint32_t)(prefixes_.size() + owners_.size()), annOff.data(),
-             ann.empty() ? nullptr : ann.data(), lfa_ ? SPF_RT_LFA : 0u, &table_)) != SPF_OK) {
+             ann.empty() ? nullptr : ann.data(), lfa_ ? SPF_RT_LFA : 0u, nsel_ ? &sd : nullptr,
+             &table_)) != SPF_OK) {
       cleanup("spf_route_table_create", s);
     }
     Counters::add("decision.route_table_create_us", usSince(tp));
@@ -352,7 +428,8 @@ AllNodesRouteTable::AllNodesRouteTable(
       cleanup("spf_route_table_run", s);
     }
     if ((s = spf_query_elapsed_ms(query_, &spfMs_)) != SPF_OK ||
-        (s = spf_route_table_elapsed_ms(table_, &routeMs_)) != SPF_OK) {
+        (s = spf_route_table_elapsed_ms(table_, &routeMs_)) != SPF_OK ||
+        (s = spf_route_table_select_elapsed_ms(table_, &selectMs_)) != SPF_OK) {
       cleanup("elapsed", s);
     }
   } catch (...) {
@@ -407,8 +484,17 @@ AllNodesRouteTable::Row AllNodesRouteTable::fetchRow(uint32_t i) const {
   r.metric.resize(P);
   r.best.resize(P);
   r.links.resize(std::max<size_t>(1, P * r.W));
-  if (int s = spf_route_table_fetch(table_, i, r.metric.data(), r.best.data(), r.links.data());
-      s != SPF_OK) {
+  if (nsel_) {
+    r.igp.resize(P);
+    std::vector<uint32_t> winners(P);
+    if (int s = spf_route_table_fetch_sel(table_, i, r.metric.data(), r.best.data(),
+                                          r.links.data(), r.igp.data(), winners.data());
+        s != SPF_OK) {
+      tableFailure("spf_route_table_fetch_sel", s);
+    }
+  } else if (int s =
+                 spf_route_table_fetch(table_, i, r.metric.data(), r.best.data(), r.links.data());
+             s != SPF_OK) {
     tableFailure("spf_route_table_fetch", s);
   }
   if (lfa_) {
@@ -437,6 +523,21 @@ RibUnicastEntry AllNodesRouteTable::materialise(
           isV4 ? l.getNhV4FromNode(node) : l.getNhV6FromNode(node), l.getIfaceFromNode(node),
           (int32_t)r.linkMetric(p, j), std::nullopt, false, l.getArea()));
     }
+  }
+  if (sel_[p]) {
+    // selectEcmpBgp (Decision.cpp:805-866) per node: the cell's best
+    // candidate, its loopback with the cell's igp as metric
+    // (PrefixState.cpp:111-126)
+    const SelCol& sc = *sel_[p];
+    for (size_t c = 0; c < announcers_[p].size(); ++c) {
+      if (announcers_[p][c].id == r.bestOf(p) && sc.via[c]) {
+        thrift::NextHopThrift via = *sc.via[c];
+        via.metric = (int32_t)r.igp[r.at(p)];
+        return RibUnicastEntry(prefixes_[p], std::move(nhs), announcers_[p][c].entry, area_,
+                               bgpDryRun_, via);
+      }
+    }
+    throw std::logic_error("AllNodesRouteTable: best candidate not in the selected column");
   }
   if (bgp_[p]) {
     // selectEcmpBgp (Decision.cpp:805-866): the host-side selection's best
@@ -1142,7 +1243,8 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
 
 AllAreasRouteTable::AllAreasRouteTable(
     const std::unordered_map<std::string, LinkState>& areas, const PrefixState& ps,
-    bool enableV4, bool computeLfa, bool bgpDryRun, bool bgpUseIgpMetric, bool prefetchAll)
+    bool enableV4, bool computeLfa, bool bgpDryRun, bool bgpUseIgpMetric, bool prefetchAll,
+    bool bgpIgpOnDevice)
     : areas_(areas),
       ps_(ps),
       enableV4_(enableV4),
@@ -1171,11 +1273,12 @@ AllAreasRouteTable::AllAreasRouteTable(
       continue; // metric 0 / 64-bit sums: this area stays on the host path
     }
     // BGP prefixes join the device table when the selection cannot depend
-    // on the node (no IGP cost in the metric vector)
-    auto t = std::make_unique<AllNodesRouteTable>(ls, ps, enableV4, computeLfa,
-                                                  multi ? &border_ : nullptr, !bgpUseIgpMetric &&
-                                                  std::getenv("OPENR_RT_BGP_HOST") == nullptr,
-                                                  bgpDryRun);
+    // on the node (no IGP cost in the metric vector), or, with
+    // bgpIgpOnDevice, as selected columns folded per node on the device
+    auto t = std::make_unique<AllNodesRouteTable>(
+        ls, ps, enableV4, computeLfa, multi ? &border_ : nullptr,
+        (!bgpUseIgpMetric || bgpIgpOnDevice) && std::getenv("OPENR_RT_BGP_HOST") == nullptr,
+        bgpDryRun, bgpUseIgpMetric);
     auto& served = served_[area];
     for (const auto& p : t->prefixes()) {
       served.insert(p);

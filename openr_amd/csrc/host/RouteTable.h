@@ -10,11 +10,14 @@
 // eligible prefix, so the routes of any node are a row read away.
 //
 // Scope (what the kernel restates, include/openr_spf.h): prefixes advertised
-// in this area only, no BGP entries, forwarding type IP with algorithm
-// SP_ECMP (Decision.cpp:395-412), v4 prefixes only with enableV4, LFA off —
-// i.e. SpfSolverImpl::selectEcmpOpenr.  routes(node) equals the unicast
-// entries SpfSolver::buildRouteDb(node) produces for those prefixes
-// (tests/test_route_table.py).
+// in this area only, forwarding type IP with algorithm SP_ECMP
+// (Decision.cpp:395-412), v4 prefixes only with enableV4 —
+// i.e. SpfSolverImpl::selectEcmpOpenr, and with bgpColumns selectEcmpBgp for
+// prefixes whose entries are all BGP with a metric vector: selected once on
+// the host without bgpUseIgpMetric, per node on the device with it
+// (spf_route_select_kernel).  routes(node) equals the unicast entries
+// SpfSolver::buildRouteDb(node) produces for those prefixes
+// (tests/test_route_table.py, tests/test_route_table_bgp_igp_gpu.py).
 //
 // MPLS (Decision.cpp:415-534, this area, LFA off): every (node label, owner)
 // pair is one more column of the same kernel pass -- a pseudo-prefix
@@ -66,10 +69,25 @@ class AllNodesRouteTable {
   // bestArea and the loopback next hop are the selection's; doNotInstall =
   // bgpDryRun.  A prefix with an announcer some node cannot reach stays on
   // the host.  diff() refuses tables with BGP columns.
+  // bgpUseIgpMetric (with bgpColumns): the selection differs per node --
+  // every candidate's vector gets an OPENR_IGP_COST entity holding -d(node,
+  // announcer) before the fold (Decision.cpp:746-766) -- so a BGP prefix
+  // becomes a SELECTED column: its in-graph announcers in fold order
+  // (without those advertising OPENR_IGP_COST, :735-744) are the candidates,
+  // compareMetricVectors runs on the host three times per ordered pair
+  // (MetricVectorUtils::bgpIgpPairCodes: the result depends on the IGP
+  // values only through the sign of their difference) and
+  // spf_route_select_kernel folds every (node, column) from the node's own
+  // distance row, skipping unreachable candidates -- no all-reachable
+  // requirement, split graphs are served.  bestPrefixEntry is the cell's
+  // best candidate's, bestNexthop its loopback with metric = the cell's igp.
+  // Left to the host: more than 32 candidates, a candidate vector with a
+  // foreign entity of priority 3500 (its order against the IGP entity is
+  // std::sort's), entries in another area.
   AllNodesRouteTable(
       const LinkState& ls, const PrefixState& ps, bool enableV4 = true, bool computeLfa = false,
       const std::unordered_set<std::string>* borderNodes = nullptr, bool bgpColumns = false,
-      bool bgpDryRun = false);
+      bool bgpDryRun = false, bool bgpUseIgpMetric = false);
   ~AllNodesRouteTable();
   AllNodesRouteTable(const AllNodesRouteTable&) = delete;
   AllNodesRouteTable& operator=(const AllNodesRouteTable&) = delete;
@@ -79,6 +97,8 @@ class AllNodesRouteTable {
   // device time of the all-sources SPF (+ next hops) and of the route kernel
   float spfMs() const { return spfMs_; }
   float routeMs() const { return routeMs_; }
+  // device time of spf_route_select_kernel (0 without selected columns)
+  float selectMs() const { return selectMs_; }
   // routes present in the table (metric != no-route), over all nodes
   uint64_t countRoutes() const;
 
@@ -142,8 +162,9 @@ class AllNodesRouteTable {
   const std::string& nodeName(uint32_t id) const { return names_.at(id); }
   // the unicast prefixes the kernel serves (routes() covers exactly these)
   const std::vector<thrift::IpPrefix>& prefixes() const { return prefixes_; }
-  // BGP prefixes among them (bgpColumns)
+  // BGP prefixes among them (bgpColumns), selected columns included
   size_t numBgpPrefixes() const { return nbgp_; }
+  size_t numSelectedColumns() const { return nsel_; }
 
  private:
   // The cells of one table row, read through the accessors below: a whole
@@ -153,6 +174,7 @@ class AllNodesRouteTable {
     std::vector<uint32_t> metric, best;
     std::vector<uint64_t> links;
     std::vector<uint32_t> lmet; // LFA: per-link metrics [cols][deg]
+    std::vector<uint32_t> igp;  // tables with selected columns: bestIgpMetric per cell
     size_t W = 0, deg = 0;
     bool sparse = false;
     std::vector<uint32_t> cols; // sparse: the columns held, ascending
@@ -203,7 +225,14 @@ class AllNodesRouteTable {
   std::vector<thrift::IpPrefix> prefixes_;
   std::vector<std::vector<Announcer>> announcers_;
   std::vector<std::optional<BgpSel>> bgp_; // per prefix (set: a BGP column)
-  size_t nbgp_{0};
+  // a selected column (bgpUseIgpMetric): parallel to the column's announcers_
+  // (= candidates, fold order)
+  struct SelCol {
+    std::vector<uint16_t> pair; // spf_route_select_desc::pair_codes of the column
+    std::vector<std::optional<thrift::NextHopThrift>> via; // the candidate's one loopback via
+  };
+  std::vector<std::optional<SelCol>> sel_; // per prefix
+  size_t nbgp_{0}, nsel_{0};
   bool bgpDryRun_{false};
   // node-label columns: column prefixes_.size() + k is owners_[k]
   struct LabelOwner {
@@ -234,7 +263,7 @@ class AllNodesRouteTable {
   spf_graph* graph_{nullptr};
   spf_query* query_{nullptr};
   spf_route_table* table_{nullptr};
-  float spfMs_{0}, routeMs_{0};
+  float spfMs_{0}, routeMs_{0}, selectMs_{0};
   bool diffed_{false};
 };
 
@@ -246,9 +275,11 @@ class AllNodesRouteTable {
 // the area's interior nodes (single area: every node, MPLS node labels
 // included); the host share is SpfSolver::buildRouteDbPartial over the
 // same LinkStates for what the kernel does not restate: border nodes (in two
-// or more areas: cross-area ECMP and drain rules), BGP prefixes (metric-
-// vector best path, Decision.cpp:714-866), SR-MPLS prefixes, prefixes a
-// border node announces, and the multi-area MPLS routes.  With
+// or more areas: cross-area ECMP and drain rules), BGP prefixes the tables
+// do not take (metric-vector best path, Decision.cpp:714-866; with
+// bgpUseIgpMetric all of them unless bgpIgpOnDevice makes them selected
+// columns of the area's table), SR-MPLS prefixes, prefixes a border node
+// announces, and the multi-area MPLS routes.  With
 // prefetchAll, every area's all-sources SPF views are computed in one
 // device batch up front, so the host share runs no SPF per node.
 class AllAreasRouteTable {
@@ -256,7 +287,7 @@ class AllAreasRouteTable {
   AllAreasRouteTable(
       const std::unordered_map<std::string, LinkState>& areas, const PrefixState& ps,
       bool enableV4 = true, bool computeLfa = false, bool bgpDryRun = false,
-      bool bgpUseIgpMetric = false, bool prefetchAll = true);
+      bool bgpUseIgpMetric = false, bool prefetchAll = true, bool bgpIgpOnDevice = false);
   ~AllAreasRouteTable();
   // nullopt iff `node` is in no area (Decision.cpp:296-302)
   std::optional<DecisionRouteDb> routeDb(const std::string& node) const;
@@ -273,6 +304,21 @@ class AllAreasRouteTable {
       n += t->numBgpPrefixes();
     }
     return n;
+  }
+  // device time of the tables' route / selection kernels, summed over areas
+  float routeMs() const {
+    float ms = 0;
+    for (const auto& [_, t] : tables_) {
+      ms += t->routeMs();
+    }
+    return ms;
+  }
+  float selectMs() const {
+    float ms = 0;
+    for (const auto& [_, t] : tables_) {
+      ms += t->selectMs();
+    }
+    return ms;
   }
 
  private:

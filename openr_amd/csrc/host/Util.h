@@ -4,6 +4,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <limits>
 #include <optional>
 #include <stdexcept>
@@ -302,6 +303,32 @@ inline CompareResult compareMetricVectors(thrift::MetricVector& l, thrift::Metri
     maybeUpdate(result, flip(resultForLoner(R[ri++])));
   }
   return result;
+}
+
+// compareMetricVectors(l + IGP(lIgp), r + IGP(rIgp)): both vectors copied and
+// given the OPENR_IGP_COST entity runBestPathSelectionBgp appends under
+// bgpUseIgpMetric (Decision.cpp:757-763), holding -igp
+inline CompareResult compareMetricVectorsWithIgp(
+    const thrift::MetricVector& l, int64_t lIgp, const thrift::MetricVector& r, int64_t rIgp) {
+  thrift::MetricVector a = l, b = r;
+  a.metrics.push_back(createMetricEntity(
+      kOpenrIgpCostType, kOpenrIgpCostPriority, thrift::CompareType::WIN_IF_NOT_PRESENT, false,
+      {-1 * lIgp}));
+  b.metrics.push_back(createMetricEntity(
+      kOpenrIgpCostType, kOpenrIgpCostPriority, thrift::CompareType::WIN_IF_NOT_PRESENT, false,
+      {-1 * rIgp}));
+  return compareMetricVectors(a, b);
+}
+
+// The three results that compare can have for vectors l and r, by the sign of
+// igp(l) - igp(r): {l closer, equal, l farther}.  The IGP entity has one
+// metric element and compareMetrics tests only < and >, so the IGP values
+// matter through that sign alone (neither vector may carry an entity of
+// priority 3500 itself).
+inline std::array<CompareResult, 3> bgpIgpPairCodes(
+    const thrift::MetricVector& l, const thrift::MetricVector& r) {
+  return {compareMetricVectorsWithIgp(l, 0, r, 1), compareMetricVectorsWithIgp(l, 0, r, 0),
+          compareMetricVectorsWithIgp(l, 1, r, 0)};
 }
 
 } // namespace MetricVectorUtils

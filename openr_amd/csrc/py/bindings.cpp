@@ -360,16 +360,30 @@ PYBIND11_MODULE(_openr_spf, m) {
            })
       .def("__len__", [](const AreaMapHolder& am) { return am.map.size(); });
 
+  // the reduction behind the device's per-node BGP selection (RouteTable.h,
+  // bgpUseIgpMetric), for CPU tests: the CompareResult values as ints
+  m.def("bgp_igp_pair_codes", [](py::handle l, py::handle r) {
+    const auto c = MetricVectorUtils::bgpIgpPairCodes(toMetricVector(l), toMetricVector(r));
+    return py::make_tuple((int)c[0], (int)c[1], (int)c[2]);
+  }, py::arg("l_mv"), py::arg("r_mv"));
+  m.def("compare_metric_vectors_with_igp", [](py::handle l, int64_t lIgp, py::handle r,
+                                              int64_t rIgp) {
+    return (int)MetricVectorUtils::compareMetricVectorsWithIgp(toMetricVector(l), lIgp,
+                                                               toMetricVector(r), rIgp);
+  }, py::arg("l_mv"), py::arg("l_igp"), py::arg("r_mv"), py::arg("r_igp"));
+
   py::class_<AllAreasRouteTable>(m, "AllAreasRouteTable")
       .def(py::init([](const AreaMapHolder& areas, const PrefixState& ps, bool enableV4, bool lfa,
-                       bool bgpDryRun, bool bgpUseIgpMetric, bool prefetchAll) {
+                       bool bgpDryRun, bool bgpUseIgpMetric, bool prefetchAll,
+                       bool bgpIgpOnDevice) {
              return std::make_unique<AllAreasRouteTable>(areas.map, ps, enableV4, lfa, bgpDryRun,
-                                                         bgpUseIgpMetric, prefetchAll);
+                                                         bgpUseIgpMetric, prefetchAll,
+                                                         bgpIgpOnDevice);
            }),
            py::arg("areas"), py::arg("prefix_state"), py::arg("enable_v4") = true,
            py::arg("lfa") = false, py::arg("bgp_dry_run") = false,
            py::arg("bgp_use_igp_metric") = false, py::arg("prefetch_all") = true,
-           py::keep_alive<1, 2>(), py::keep_alive<1, 3>())
+           py::arg("bgp_igp_on_device") = false, py::keep_alive<1, 2>(), py::keep_alive<1, 3>())
       .def("route_db", [](const AllAreasRouteTable& t, const std::string& node) -> py::object {
         auto db = t.routeDb(node);
         if (!db) {
@@ -381,6 +395,24 @@ PYBIND11_MODULE(_openr_spf, m) {
       .def_property_readonly("last_host_routes", &AllAreasRouteTable::lastHostRoutes)
       .def_property_readonly("num_tables", &AllAreasRouteTable::numTables)
       .def_property_readonly("bgp_device_prefixes", &AllAreasRouteTable::numBgpDevicePrefixes)
+      .def("route_db_loop_timed", [](const AllAreasRouteTable& t,
+                                     const std::vector<std::string>& nodes) {
+        // routeDb(node) for every listed node in C++, no Python conversion:
+        // (routes from the device tables, routes from the host share, wall us)
+        size_t table = 0, host = 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (const std::string& node : nodes) {
+          const auto db = t.routeDb(node);
+          table += t.lastTableRoutes();
+          host += t.lastHostRoutes();
+        }
+        const double us = std::chrono::duration<double, std::micro>(
+                              std::chrono::steady_clock::now() - t0)
+                              .count();
+        return py::make_tuple((long)table, (long)host, us);
+      })
+      .def_property_readonly("route_ms", &AllAreasRouteTable::routeMs)
+      .def_property_readonly("select_ms", &AllAreasRouteTable::selectMs)
       .def("is_border", &AllAreasRouteTable::isBorder);
 
   py::class_<AllSourcesTable>(m, "AllSourcesTable")

@@ -6283,8 +6283,22 @@ struct RouteTableArgs {
   const uint64_t* lm_off;
   uint32_t* lmet_out;
   uint32_t Vp, P, nq, lfa;
+  // selected columns (spf_route_select_kernel ran first; the <true> instance
+  // only): column p is selected column sel_of[p] (kInf32: none); its cell of
+  // row q has winners word sel_w[q * S + k] over the column's announcers
+  // (bit i = announcer ann_off[p] + i; 0 = no route) and best sel_best[..]
+  const uint32_t* sel_of;
+  const uint32_t* sel_w;
+  const uint32_t* sel_best;
+  uint32_t S;
 };
 
+// SEL: the table has selected columns (BGP best path per node, see
+// spf_route_select_kernel).  A selected column's cell is the same
+// computation over the announcers in the cell's winners word (drained filter
+// already applied there), with `best` the selection's.  The <false> instance
+// is the kernel as it was: every SEL branch is compiled out.
+template <bool SEL>
 __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) {
   __shared__ uint32_t st_nbr[kRtStage];
   __shared__ uint32_t st_w[kRtStage];
@@ -6320,7 +6334,26 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
       const uint32_t lo = a.ann_off[p], hi = a.ann_off[p + 1];
       bool self = false;
       uint32_t best = kInf32, reach = 0, undrained = 0;
-      for (uint32_t i = lo; i < hi; ++i) {
+      // winners word of a selected column (else every announcer)
+      [[maybe_unused]] uint32_t wm = ~0u;
+      [[maybe_unused]] bool selc = false;
+      if constexpr (SEL) {
+        const uint32_t k = a.sel_of[p];
+        if (k != kInf32) {
+          selc = true;
+          wm = a.sel_w[(size_t)q * a.S + k];
+          best = a.sel_best[(size_t)q * a.S + k];
+          reach = wm != 0; // winners are reachable; self and drained: decided there
+        }
+      }
+      auto in_w = [&](uint32_t i) -> bool {
+        if constexpr (SEL) {
+          return (wm >> ((i - lo) & 31u)) & 1u;
+        } else {
+          return true;
+        }
+      };
+      for (uint32_t i = lo; i < hi && !selc; ++i) {
         const uint32_t x = a.ann[i];
         self |= x == s;
         if (d[x] == kInf32) {
@@ -6348,7 +6381,7 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
       uint32_t mn = kInf32;
       for (uint32_t i = lo; i < hi; ++i) {
         const uint32_t x = a.ann[i];
-        if (d[x] != kInf32 && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+        if (d[x] != kInf32 && in_w(i) && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
           mn = min(mn, d[x]);
         }
       }
@@ -6364,7 +6397,7 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
         }
         for (uint32_t i = lo; i < hi; ++i) {
           const uint32_t x = a.ann[i];
-          if (d[x] == mn && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+          if (d[x] == mn && in_w(i) && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
 #pragma unroll
             for (uint32_t k = 0; k < kRtMaskWords; ++k) {
               if (k < W) {
@@ -6394,7 +6427,8 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
               const uint64_t lim = (uint64_t)mn + st_dns[j];
               for (uint32_t i = lo; i < hi; ++i) {
                 const uint32_t x = a.ann[i];
-                if (d[x] == kInf32 || (filt && !((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+                if (d[x] == kInf32 || !in_w(i) ||
+                    (filt && !((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
                   continue;
                 }
                 const uint32_t dx = rn[x];
@@ -6443,7 +6477,7 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
           uint64_t mm = 0;
           for (uint32_t i = lo; i < hi && !mm; ++i) {
             const uint32_t x = a.ann[i];
-            if (d[x] == mn && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+            if (d[x] == mn && in_w(i) && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
               mm = (nh_load(nhq, NB, W, x, sl >> 6) >> (sl & 63)) & 1ull;
             }
           }
@@ -6451,6 +6485,105 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
         }
         lkp[k] = out;
       }
+    }
+  }
+}
+
+// BGP best path per node with the IGP cost in the metric vector
+// (spf_route_table_create_sel; SpfSolverImpl::runBestPathSelectionBgp,
+// Decision.cpp:714-803, with bgpUseIgpMetric :746-766, then selectEcmpBgp
+// :805-866 up to the next-hop computation): for source row q (node s) and
+// selected column k, fold the column's candidates in list order, skipping
+// unreachable ones (:726-733).  The compare of candidate i against the
+// current best b was reduced on the host to three CompareResult codes per
+// ordered pair (b < i), chosen here by the sign of d(s, i) - d(s, b): entry
+// i(i-1)/2 + b of the column's pair table, bits 0-2 = i closer, 3-5 = equal,
+// 6-8 = i farther.  igp = min d(s, c) over every reachable candidate, losers
+// included (bestIgpMetric).  After the fold maybeFilterDrainedNodes
+// (:651-666) on the winners word through the transit bits; no route if the
+// fold met TIE / ERROR (:784-792), no winner, s among the filtered winners,
+// or the best candidate has no loopback (flag bit 0 clear; :829-838).
+// Outputs per cell: filtered winners word (bit i = candidate i; 0 = no
+// route), best (node id of the fold's best; not re-chosen by the drain
+// filter) and igp -- UINT32_MAX both when there is no route.
+// Launch shape of spf_route_table_kernel: one workgroup per row, lanes
+// striding over the selected columns.  A lane owns its column, so candidate
+// lists and pair tables are per-lane reads of small read-only arrays (cache
+// resident across rows); only the row's source is wave-uniform and comes
+// through the constant path.  Distance gathers stay inside the row.
+enum : uint32_t {
+  kCmpWinner = 0, // MetricVectorUtils::CompareResult, in its order
+  kCmpTieWinner = 1,
+  kCmpTie = 2,
+  kCmpTieLooser = 3,
+  kCmpLooser = 4,
+  kCmpError = 5
+};
+struct RouteSelectArgs {
+  const uint32_t* src;
+  const uint32_t* dist; // query rows, stride Vp
+  const uint32_t* trbits;
+  const uint32_t* ann_off; // the table's [P+1]
+  const uint32_t* ann;
+  const uint32_t* sel_col;  // [S] column of selected column k
+  const uint64_t* pair_off; // [S+1]
+  const uint16_t* pair;
+  const uint8_t* cflags; // parallel to ann
+  uint32_t* w_out;    // [nq][S]
+  uint32_t* best_out; // [nq][S]
+  uint32_t* igp_out;  // [nq][S]
+  uint32_t Vp, S, nq;
+};
+
+__global__ __launch_bounds__(256) void spf_route_select_kernel(RouteSelectArgs a) {
+  for (uint32_t q = blockIdx.x; q < a.nq; q += gridDim.x) {
+    const uint32_t s = nl_const(a.src)[q];
+    const uint32_t* d = a.dist + (size_t)q * a.Vp;
+    for (uint32_t k = threadIdx.x; k < a.S; k += blockDim.x) {
+      const uint32_t p = a.sel_col[k];
+      const uint32_t lo = a.ann_off[p], n = a.ann_off[p + 1] - lo; // n <= 32 (checked at create)
+      const uint16_t* pt = a.pair + a.pair_off[k];
+      uint32_t best = kInf32, dbest = 0, igp = kInf32;
+      uint32_t mask = 0, trm = 0, selfm = 0;
+      bool ok = true;
+      for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t x = a.ann[lo + i];
+        const uint32_t dx = d[x];
+        if (dx == kInf32) {
+          continue;
+        }
+        igp = min(igp, dx);
+        trm |= ((a.trbits[x >> 5] >> (x & 31)) & 1u) << i;
+        selfm |= (uint32_t)(x == s) << i;
+        uint32_t code = kCmpWinner;
+        if (best != kInf32) {
+          const uint32_t e = pt[i * (i - 1) / 2 + best];
+          code = (e >> (dx < dbest ? 0u : dx == dbest ? 3u : 6u)) & 7u;
+        }
+        if (code == kCmpTie || code >= kCmpError) {
+          ok = false;
+          break;
+        }
+        if (code == kCmpWinner) {
+          mask = 0;
+        }
+        if (code <= kCmpTieWinner) {
+          best = i;
+          dbest = dx;
+        }
+        if (code <= kCmpTieLooser) {
+          mask |= 1u << i;
+        }
+      }
+      const uint32_t filt = (mask & trm) ? (mask & trm) : mask;
+      bool route = ok && filt != 0 && !(filt & selfm); // (filt != 0: best is a candidate)
+      if (route) {
+        route = a.cflags[lo + best] & 1u;
+      }
+      const size_t o = (size_t)q * a.S + k;
+      a.w_out[o] = route ? filt : 0u;
+      a.best_out[o] = route ? a.ann[lo + best] : kInf32;
+      a.igp_out[o] = route ? igp : kInf32;
     }
   }
 }
@@ -14409,6 +14542,17 @@ struct spf_route_table {
   uint32_t *d_gc_idx = nullptr, *d_gc_out = nullptr, *d_gc_lmet = nullptr;
   uint64_t *d_gc_pos = nullptr, *d_gc_links = nullptr;
   size_t gc_idx_cap = 0, gc_out_cap = 0, gc_lmet_cap = 0, gc_pos_cap = 0, gc_links_cap = 0;
+  // selected columns (spf_route_table_create_sel): S of them, sel_col[k] the
+  // column; per-cell winners / best / igp are [nq][S]; evs0 .. ev0 times the
+  // selection kernel
+  uint32_t S = 0;
+  std::vector<uint32_t> sel_col;
+  uint32_t *d_sel_col = nullptr, *d_sel_of = nullptr, *d_sel_w = nullptr, *d_sel_best = nullptr,
+           *d_sel_igp = nullptr;
+  uint64_t* d_pair_off = nullptr;
+  uint16_t* d_pair = nullptr;
+  uint8_t* d_cflags = nullptr;
+  hipEvent_t evs0 = nullptr;
 };
 
 namespace {
@@ -14424,10 +14568,15 @@ void free_route_table(spf_route_table* t) {
                   (void*)t->d_gone, (void*)t->d_pk_cnt, (void*)t->d_pk_cell, (void*)t->d_pk_lmet,
                   (void*)t->d_pk_gone, (void*)t->d_pk_off, (void*)t->d_pk_links,
                   (void*)t->d_gc_idx, (void*)t->d_gc_out, (void*)t->d_gc_lmet, (void*)t->d_gc_pos,
-                  (void*)t->d_gc_links}) {
+                  (void*)t->d_gc_links, (void*)t->d_sel_col, (void*)t->d_sel_of,
+                  (void*)t->d_sel_w, (void*)t->d_sel_best, (void*)t->d_sel_igp,
+                  (void*)t->d_pair_off, (void*)t->d_pair, (void*)t->d_cflags}) {
     if (p) {
       (void)hipFree(p);
     }
+  }
+  if (t->evs0) {
+    (void)hipEventDestroy(t->evs0);
   }
   if (t->ev0) {
     (void)hipEventDestroy(t->ev0);
@@ -14559,6 +14708,84 @@ int spf_route_table_create_ex(
   return SPF_OK;
 }
 
+int spf_route_table_create_sel(
+    spf_query* q, uint32_t num_prefixes, const uint32_t* ann_offsets,
+    const uint32_t* announcers, uint32_t flags, const spf_route_select_desc* sel,
+    spf_route_table** out) {
+  if (!sel || sel->num_selected == 0) {
+    return spf_route_table_create_ex(q, num_prefixes, ann_offsets, announcers, flags, out);
+  }
+  if (!out) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  *out = nullptr;
+  const uint32_t S = sel->num_selected;
+  if (!sel->columns || !sel->pair_offsets || !sel->cand_flags || !ann_offsets) {
+    return fail(SPF_E_INVALID, "null selection array");
+  }
+  if (sel->pair_offsets[0] != 0) {
+    return fail(SPF_E_INVALID, "pair_offsets[0] != 0");
+  }
+  // (create_ex checks ann_offsets again; these reads need it monotone first)
+  for (uint32_t p = 0; p < num_prefixes; ++p) {
+    if (ann_offsets[p + 1] < ann_offsets[p]) {
+      return fail(SPF_E_INVALID, "ann_offsets not monotone");
+    }
+  }
+  std::vector<uint32_t> sel_of(num_prefixes, kInf32);
+  for (uint32_t k = 0; k < S; ++k) {
+    const uint32_t p = sel->columns[k];
+    if (p >= num_prefixes || sel_of[p] != kInf32) {
+      return fail(SPF_E_INVALID, "selected column out of range or listed twice");
+    }
+    sel_of[p] = k;
+    const uint64_t n = ann_offsets[p + 1] - ann_offsets[p];
+    if (n > 32) {
+      return fail(SPF_E_INVALID, "a selected column has more than 32 candidates");
+    }
+    if (sel->pair_offsets[k + 1] < sel->pair_offsets[k] ||
+        sel->pair_offsets[k + 1] - sel->pair_offsets[k] < n * (n - (n ? 1 : 0)) / 2) {
+      return fail(SPF_E_INVALID, "pair table shorter than n(n-1)/2");
+    }
+  }
+  const uint64_t npair = sel->pair_offsets[S];
+  if (npair && !sel->pair_codes) {
+    return fail(SPF_E_INVALID, "null pair_codes");
+  }
+  spf_route_table* t = nullptr;
+  if (int st = spf_route_table_create_ex(q, num_prefixes, ann_offsets, announcers, flags, &t);
+      st != SPF_OK) {
+    return st;
+  }
+  auto bail = [&](int st) {
+    free_route_table(t);
+    return st;
+  };
+  t->S = S;
+  t->sel_col.assign(sel->columns, sel->columns + S);
+  const uint32_t na = ann_offsets[num_prefixes];
+  const size_t cells = (size_t)q->nq * S;
+  int st = SPF_OK;
+  if ((st = dev_upload(&t->d_sel_col, sel->columns, (size_t)S)) ||
+      (st = dev_upload(&t->d_sel_of, sel_of.data(), sel_of.size())) ||
+      (st = dev_upload(&t->d_pair_off, sel->pair_offsets, (size_t)S + 1)) ||
+      (st = dev_upload(&t->d_pair, sel->pair_codes, (size_t)npair)) ||
+      (st = dev_upload(&t->d_cflags, sel->cand_flags, (size_t)na))) {
+    return bail(st);
+  }
+  if (cells &&
+      (hipMalloc((void**)&t->d_sel_w, cells * 4) != hipSuccess ||
+       hipMalloc((void**)&t->d_sel_best, cells * 4) != hipSuccess ||
+       hipMalloc((void**)&t->d_sel_igp, cells * 4) != hipSuccess)) {
+    return bail(fail(SPF_E_NOMEM, "selection cells"));
+  }
+  if (hipEventCreate(&t->evs0) != hipSuccess) {
+    return bail(fail(SPF_E_DEVICE, "hipEventCreate"));
+  }
+  *out = t;
+  return SPF_OK;
+}
+
 int spf_route_table_destroy(spf_route_table* t) {
   SPF_ABI_RANGE("spf_route_table_destroy");
   free_route_table(t);
@@ -14576,6 +14803,30 @@ int spf_route_table_run(spf_route_table* t) {
   }
   spf_graph* g = q->g;
   HIP_TRY(hipSetDevice(g->device));
+  const uint32_t grid = std::min<uint32_t>(q->nq, (uint32_t)g->num_cus * 8);
+  if (t->S) {
+    HIP_TRY(hipEventRecord(t->evs0, g->stream));
+    if (q->nq) {
+      RouteSelectArgs sa;
+      sa.src = q->d_src;
+      sa.dist = (const uint32_t*)q->d_dist;
+      sa.trbits = g->d_tr;
+      sa.ann_off = t->d_ann_off;
+      sa.ann = t->d_ann;
+      sa.sel_col = t->d_sel_col;
+      sa.pair_off = t->d_pair_off;
+      sa.pair = t->d_pair;
+      sa.cflags = t->d_cflags;
+      sa.w_out = t->d_sel_w;
+      sa.best_out = t->d_sel_best;
+      sa.igp_out = t->d_sel_igp;
+      sa.Vp = q->Vp;
+      sa.S = t->S;
+      sa.nq = q->nq;
+      SPF_LAUNCH(spf_route_select_kernel, dim3(grid), dim3(256), 0, g->stream, sa);
+      HIP_TRY(hipGetLastError());
+    }
+  }
   HIP_TRY(hipEventRecord(t->ev0, g->stream));
   if (q->nq && t->P) {
     RouteTableArgs a;
@@ -14603,8 +14854,15 @@ int spf_route_table_run(spf_route_table* t) {
     a.Vp = q->Vp;
     a.P = t->P;
     a.nq = q->nq;
-    const uint32_t grid = std::min<uint32_t>(q->nq, (uint32_t)g->num_cus * 8);
-    SPF_LAUNCH(spf_route_table_kernel, dim3(grid), dim3(256), 0, g->stream, a);
+    a.sel_of = t->d_sel_of;
+    a.sel_w = t->d_sel_w;
+    a.sel_best = t->d_sel_best;
+    a.S = t->S;
+    if (t->S) {
+      SPF_LAUNCH(spf_route_table_kernel<true>, dim3(grid), dim3(256), 0, g->stream, a);
+    } else {
+      SPF_LAUNCH(spf_route_table_kernel<false>, dim3(grid), dim3(256), 0, g->stream, a);
+    }
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(t->ev1, g->stream));
@@ -14620,6 +14878,19 @@ int spf_route_table_elapsed_ms(spf_route_table* t, float* ms) {
   }
   HIP_TRY(hipEventSynchronize(t->ev1));
   HIP_TRY(hipEventElapsedTime(ms, t->ev0, t->ev1));
+  return SPF_OK;
+}
+
+int spf_route_table_select_elapsed_ms(spf_route_table* t, float* ms) {
+  if (!t || !ms || !t->ran) {
+    return fail(SPF_E_INVALID, "no run to time");
+  }
+  *ms = 0.f;
+  if (!t->S) {
+    return SPF_OK;
+  }
+  HIP_TRY(hipEventSynchronize(t->ev0));
+  HIP_TRY(hipEventElapsedTime(ms, t->evs0, t->ev0));
   return SPF_OK;
 }
 
@@ -14654,6 +14925,34 @@ int spf_route_table_fetch(
       return fail(SPF_E_INVALID, "null links");
     }
     HIP_TRY(hipMemcpy(links, t->d_links + t->lk_off[i], nw * 8, hipMemcpyDeviceToHost));
+  }
+  return SPF_OK;
+}
+
+int spf_route_table_fetch_sel(
+    spf_route_table* t, uint32_t i, uint32_t* metric, uint32_t* best, uint64_t* links,
+    uint32_t* igp, uint32_t* winners) {
+  if (int st = spf_route_table_fetch(t, i, metric, best, links); st != SPF_OK) {
+    return st;
+  }
+  if (t->P == 0) {
+    return SPF_OK;
+  }
+  if (!igp || !winners) {
+    return fail(SPF_E_INVALID, "null igp / winners");
+  }
+  std::fill(igp, igp + t->P, kInf32);
+  std::fill(winners, winners + t->P, 0u);
+  if (!t->S) {
+    return SPF_OK;
+  }
+  std::vector<uint32_t> w(t->S), g(t->S);
+  const size_t o = (size_t)i * t->S;
+  HIP_TRY(hipMemcpy(w.data(), t->d_sel_w + o, (size_t)t->S * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(g.data(), t->d_sel_igp + o, (size_t)t->S * 4, hipMemcpyDeviceToHost));
+  for (uint32_t k = 0; k < t->S; ++k) {
+    winners[t->sel_col[k]] = w[k];
+    igp[t->sel_col[k]] = g[k];
   }
   return SPF_OK;
 }
