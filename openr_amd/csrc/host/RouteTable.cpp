@@ -25,7 +25,356 @@ int64_t usSince(std::chrono::steady_clock::time_point t0) {
       std::string("openr_spf: ") + what + ": " + spf_error_string(status) + " (" +
       spf_last_error_detail() + ")");
 }
+
+// f(index) for every set bit of words[0 .. n), ascending
+template <class F>
+void forEachSetBit(const uint64_t* words, size_t n, F&& f) {
+  for (size_t k = 0; k < n; ++k) {
+    for (uint64_t m = words[k]; m; m &= m - 1) {
+      f(k * 64 + (size_t)__builtin_ctzll(m));
+    }
+  }
+}
 } // namespace
+
+// eligibility and announcers of prefix i (Decision.cpp:313-412 restricted to
+// selectEcmpOpenr, and with bgpColumns selectEcmpBgp): read-only PrefixState
+// lookups, one prefix per call on the host pool
+void AllNodesRouteTable::scanPrefix(PrefixScan& s, size_t i) const {
+  const LinkState& ls = s.ls;
+  const PrefixState& ps = s.ps;
+  const auto* borderNodes = s.borderNodes;
+  const bool bgpColumns = s.bgpColumns, bgpUseIgpMetric = s.bgpUseIgpMetric;
+  auto& keep = s.keep;
+  auto& anns = s.anns;
+  auto& bgpAll = s.bgpAll;
+  auto& sels = s.sels;
+  auto& selCols = s.selCols;
+  const auto& prefix = *s.items[i].first;
+  const auto& entries = *s.items[i].second;
+  bool otherArea = false, bgp = false, nonBgp = false, missingMv = false, inArea = false,
+       borderAnn = false;
+  for (const auto& [node, byArea] : entries) {
+    for (const auto& [area, entry] : byArea) {
+      otherArea |= area != area_;
+      inArea |= area == area_;
+      borderAnn |= area == area_ && borderNodes && borderNodes->count(node);
+      const bool isBgp = entry.type == thrift::PrefixType::BGP;
+      bgp |= isBgp;
+      nonBgp |= !isBgp;
+      missingMv |= isBgp && !entry.mv.has_value();
+    }
+  }
+  if ((bgp && !bgpColumns) || (bgp && (nonBgp || missingMv)) || entries.empty() ||
+      (otherArea && !borderNodes) || !inArea || borderAnn) {
+    return;
+  }
+  if (prefix.prefixAddress.addr.size() == 4 && !enableV4_) {
+    return;
+  }
+  if (getPrefixForwardingType(entries) != thrift::PrefixForwardingType::IP ||
+      getPrefixForwardingAlgorithm(entries) != thrift::PrefixForwardingAlgorithm::SP_ECMP) {
+    return;
+  }
+  if (!bgp) {
+    for (const auto& [node, byArea] : entries) {
+      auto it = ids_.find(node);
+      auto ea = byArea.find(area_);
+      if (it == ids_.end() || ea == byArea.end()) {
+        continue; // not in the graph / announced in another area: never reachable
+      }
+      anns[i].push_back(Announcer{it->second, ea->second});
+    }
+    keep[i] = 1;
+    return;
+  }
+  if (otherArea) {
+    return; // (interior-node tables of several areas: BGP stays on the host)
+  }
+  namespace mvu = MetricVectorUtils;
+  if (bgpUseIgpMetric) {
+    // a selected column: the fold runs per node on the device
+    // (spf_route_select_kernel).  Candidates = in-graph announcers in
+    // fold order, without those that advertise OPENR_IGP_COST
+    // (Decision.cpp:735-744: skipped before bestIgpMetric sees them)
+    SelCol sc;
+    std::vector<const thrift::MetricVector*> mvs;
+    const bool isV4 = prefix.prefixAddress.addr.size() == 4;
+    for (const auto& [node, byArea] : entries) {
+      for (const auto& [area, entry] : byArea) {
+        auto it = ids_.find(node);
+        if (it == ids_.end()) {
+          continue; // not in the graph: unreachable from every node
+        }
+        const thrift::MetricVector& mv = entry.mv.value();
+        if (mvu::getMetricEntityByType(mv, mvu::kOpenrIgpCostType)) {
+          continue;
+        }
+        for (const auto& me : mv.metrics) {
+          if (me.priority == mvu::kOpenrIgpCostPriority) {
+            return; // std::sort leaves its order against the IGP entity open: host
+          }
+        }
+        anns[i].push_back(Announcer{it->second, entry});
+        mvs.push_back(&mv);
+        auto vias = ps.getLoopbackVias({node}, isV4, std::nullopt);
+        sc.via.push_back(vias.size() == 1 ? std::optional<thrift::NextHopThrift>(vias[0])
+                                          : std::nullopt);
+      }
+    }
+    if (mvs.size() > 32) {
+      anns[i].clear();
+      return; // the winners word has 32 bits: host
+    }
+    for (size_t c = 1; c < mvs.size(); ++c) {
+      for (size_t b = 0; b < c; ++b) {
+        const auto codes = mvu::bgpIgpPairCodes(*mvs[c], *mvs[b]);
+        sc.pair.push_back((uint16_t)((unsigned)codes[0] | ((unsigned)codes[1] << 3) |
+                                     ((unsigned)codes[2] << 6)));
+      }
+    }
+    selCols[i] = std::move(sc);
+    keep[i] = 3;
+    return;
+  }
+  // runBestPathSelectionBgp (Decision.cpp:714-803) without the IGP
+  // cost, every in-graph announcer reachable: entries in map order
+  std::optional<thrift::MetricVector> bestVector;
+  std::set<std::string> winners;
+  std::string bestNode, bestArea;
+  for (const auto& [node, byArea] : entries) {
+    for (const auto& [area, entry] : byArea) {
+      auto it = ids_.find(node);
+      if (it == ids_.end()) {
+        continue; // not in the graph: unreachable from every node
+      }
+      bgpAll[i].push_back(it->second);
+      const thrift::MetricVector& mvIn = entry.mv.value();
+      if (mvu::getMetricEntityByType(mvIn, mvu::kOpenrIgpCostType)) {
+        continue;
+      }
+      thrift::MetricVector mv = mvIn;
+      mvu::CompareResult cmp = mvu::CompareResult::WINNER;
+      if (bestVector) {
+        cmp = mvu::compareMetricVectors(mv, *bestVector);
+      }
+      switch (cmp) {
+      case mvu::CompareResult::WINNER:
+        winners.clear();
+        [[fallthrough]];
+      case mvu::CompareResult::TIE_WINNER:
+        bestVector = std::move(mv);
+        bestNode = node;
+        bestArea = area;
+        [[fallthrough]];
+      case mvu::CompareResult::TIE_LOOSER:
+        winners.insert(node);
+        break;
+      case mvu::CompareResult::TIE:
+      case mvu::CompareResult::ERROR:
+        // cannot order: no route at any node
+        sels[i] = BgpSel{};
+        keep[i] = 2;
+        return;
+      default:
+        break;
+      }
+    }
+  }
+  BgpSel sel;
+  if (!winners.empty()) {
+    // maybeFilterDrainedNodes (Decision.cpp:651-666)
+    std::set<std::string> undrained;
+    for (const auto& w : winners) {
+      if (!ls.isNodeOverloaded(w)) {
+        undrained.insert(w);
+      }
+    }
+    const auto& use = undrained.empty() ? winners : undrained;
+    auto vias = ps.getLoopbackVias({bestNode}, prefix.prefixAddress.addr.size() == 4,
+                                   std::nullopt);
+    if (vias.size() == 1) {
+      sel.bestEntry = entries.at(bestNode).at(bestArea);
+      sel.bestArea = bestArea;
+      sel.bestNexthop = vias.at(0);
+      for (const auto& w : use) {
+        anns[i].push_back(Announcer{ids_.at(w), entries.at(w).at(area_)});
+      }
+    }
+  }
+  sels[i] = std::move(sel);
+  keep[i] = 2;
+}
+
+// BGP columns need every in-graph announcer reachable from every node:
+// reachability is symmetric here (links are up in both directions and a
+// path's interior nodes are the same either way), so the announcer's
+// own row answers for every node
+void AllNodesRouteTable::dropUnreachableBgp(PrefixScan& s) const {
+  const uint32_t V = (uint32_t)names_.size();
+  std::unordered_map<uint32_t, bool> reachesAll;
+  std::vector<uint32_t> rowBuf(V);
+  for (size_t i = 0; i < s.items.size(); ++i) {
+    if (s.keep[i] != 2) {
+      continue;
+    }
+    for (const uint32_t a : s.bgpAll[i]) {
+      auto it = reachesAll.find(a);
+      if (it == reachesAll.end()) {
+        if (int st = spf_query_fetch_rows(query_.get(), a, 1, rowBuf.data(), (size_t)V * 4, 0);
+            st != SPF_OK) {
+          tableFailure("spf_query_fetch_rows", st);
+        }
+        const bool all = std::all_of(rowBuf.begin(), rowBuf.end(),
+                                     [](uint32_t x) { return x != 0xFFFFFFFFu; });
+        it = reachesAll.emplace(a, all).first;
+      }
+      if (!it->second) {
+        s.keep[i] = 0; // some node does not reach this announcer: the host path
+        break;
+      }
+    }
+  }
+}
+
+// prefix order: by first announcer id, so neighbouring lanes of the
+// kernel read neighbouring distance / next-hop mask words of a row
+void AllNodesRouteTable::orderColumns(std::vector<uint32_t>& annOff, std::vector<uint32_t>& ann) {
+  std::vector<uint32_t> order(prefixes_.size());
+  for (uint32_t i = 0; i < order.size(); ++i) {
+    order[i] = i;
+  }
+  auto key = [&](uint32_t i) {
+    return announcers_[i].empty() ? 0xFFFFFFFFu : announcers_[i][0].id;
+  };
+  std::stable_sort(order.begin(), order.end(),
+                   [&](uint32_t x, uint32_t y) { return key(x) < key(y); });
+  std::vector<thrift::IpPrefix> px;
+  std::vector<std::vector<Announcer>> ax;
+  std::vector<std::optional<BgpSel>> bx;
+  std::vector<std::optional<SelCol>> sx;
+  sx.reserve(order.size());
+  px.reserve(order.size());
+  ax.reserve(order.size());
+  bx.reserve(order.size());
+  for (uint32_t i : order) {
+    px.push_back(std::move(prefixes_[i]));
+    ax.push_back(std::move(announcers_[i]));
+    bx.push_back(std::move(bgp_[i]));
+    sx.push_back(std::move(sel_[i]));
+  }
+  sel_ = std::move(sx);
+  prefixes_ = std::move(px);
+  announcers_ = std::move(ax);
+  bgp_ = std::move(bx);
+  for (const auto& as : announcers_) {
+    for (const auto& a : as) {
+      ann.push_back(a.id);
+    }
+    annOff.push_back((uint32_t)ann.size());
+  }
+}
+
+// node-label columns (Decision.cpp:415-481): one pseudo-prefix per (valid
+// label, owner in the graph), owners of a label by name; the cell of node
+// s is getNextHopsWithMetric(s, {owner}) with LFA off
+void AllNodesRouteTable::addNodeLabelColumns(
+    const LinkState& ls, std::vector<uint32_t>& annOff, std::vector<uint32_t>& ann) {
+  // (label, owner id) sorted: labels ascending, owners by name (ids are
+  // name ranks) -- the order of a label -> sorted names map, without one
+  std::vector<std::pair<int32_t, uint32_t>> lab;
+  lab.reserve(names_.size());
+  nodeLabel_.assign(names_.size(), 0);
+  for (const auto& [node, db] : ls.getAdjacencyDatabases()) {
+    if (db.nodeLabel == 0 || !isMplsLabelValid(db.nodeLabel)) {
+      continue;
+    }
+    auto it = ids_.find(node);
+    if (it != ids_.end()) {
+      lab.emplace_back(db.nodeLabel, it->second);
+      nodeLabel_[it->second] = db.nodeLabel;
+    }
+  }
+  std::sort(lab.begin(), lab.end());
+  for (size_t i = 0; i < lab.size();) {
+    auto& cols =
+        labelCols_.emplace_hint(labelCols_.end(), lab[i].first, std::vector<uint32_t>{})->second;
+    size_t j = i;
+    for (; j < lab.size() && lab[j].first == lab[i].first; ++j) {
+      cols.push_back((uint32_t)(prefixes_.size() + owners_.size()));
+      owners_.push_back(LabelOwner{lab[j].first, lab[j].second});
+      ann.push_back(lab[j].second);
+      annOff.push_back((uint32_t)ann.size());
+    }
+    i = j;
+  }
+}
+
+// adjacency labels of every node (Decision.cpp:511-534), values copied
+// (independent per node: read-only LinkState lookups on the host pool)
+void AllNodesRouteTable::collectAdjLabels(const LinkState& ls) {
+  adjLabels_.resize(names_.size());
+  parallelFor(names_.size(), hostThreads(names_.size(), 256), [&](size_t i, unsigned) {
+    for (const auto& link : ls.linksFromNode(names_[i])) {
+      const int32_t label = link->getAdjLabelFromNode(names_[i]);
+      if (label == 0 || !isMplsLabelValid(label)) {
+        continue;
+      }
+      adjLabels_[i].push_back(AdjLabel{
+          label, link->getNhV6FromNode(names_[i]), link->getIfaceFromNode(names_[i]),
+          (int32_t)link->getMetricFromNode(names_[i]), link->getArea()});
+    }
+  }, 64);
+}
+
+// selected columns (pair tables and loopback bits parallel to ann), then the
+// engine's table over every column, created and run
+void AllNodesRouteTable::createAndRunTable(
+    const std::vector<uint32_t>& annOff, const std::vector<uint32_t>& ann) {
+  auto tp = std::chrono::steady_clock::now();
+  std::vector<uint32_t> selColumns;
+  std::vector<uint64_t> pairOff{0};
+  std::vector<uint16_t> pairCodes;
+  std::vector<uint8_t> candFlags(ann.size(), 0);
+  for (size_t p = 0; p < prefixes_.size(); ++p) {
+    if (!sel_[p]) {
+      continue;
+    }
+    selColumns.push_back((uint32_t)p);
+    pairCodes.insert(pairCodes.end(), sel_[p]->pair.begin(), sel_[p]->pair.end());
+    pairOff.push_back(pairCodes.size());
+    for (size_t c = 0; c < sel_[p]->via.size(); ++c) {
+      candFlags[annOff[p] + c] = sel_[p]->via[c] ? 1 : 0;
+    }
+  }
+  nsel_ = selColumns.size();
+  spf_route_select_desc sd{};
+  sd.num_selected = (uint32_t)selColumns.size();
+  sd.columns = selColumns.data();
+  sd.pair_offsets = pairOff.data();
+  sd.pair_codes = pairCodes.data();
+  sd.cand_flags = candFlags.data();
+  int s = SPF_OK;
+  spf_route_table* table = nullptr;
+  if ((s = spf_route_table_create_sel(
+           query_.get(), (uint32_t)(prefixes_.size() + owners_.size()), annOff.data(),
+           ann.empty() ? nullptr : ann.data(), lfa_ ? SPF_RT_LFA : 0u, nsel_ ? &sd : nullptr,
+           &table)) != SPF_OK) {
+    tableFailure("spf_route_table_create", s);
+  }
+  table_.reset(table);
+  Counters::add("decision.route_table_create_us", usSince(tp));
+  tp = std::chrono::steady_clock::now();
+  if ((s = spf_route_table_run(table_.get())) != SPF_OK) {
+    tableFailure("spf_route_table_run", s);
+  }
+  if ((s = spf_query_elapsed_ms(query_.get(), &spfMs_)) != SPF_OK ||
+      (s = spf_route_table_elapsed_ms(table_.get(), &routeMs_)) != SPF_OK ||
+      (s = spf_route_table_select_elapsed_ms(table_.get(), &selectMs_)) != SPF_OK) {
+    tableFailure("elapsed", s);
+  }
+  Counters::add("decision.route_table_run_us", usSince(tp));
+}
 
 AllNodesRouteTable::AllNodesRouteTable(
     const LinkState& ls, const PrefixState& ps, bool enableV4, bool computeLfa,
@@ -60,397 +409,74 @@ AllNodesRouteTable::AllNodesRouteTable(
   d.node_overloaded = eng.overloaded.data();
   d.num_links = (uint32_t)eng.links.size();
   d.device = getSpfDevice();
-  if (int s = spf_graph_create(&d, &graph_); s != SPF_OK) {
+  // (a failure below throws: the handles created so far are members already)
+  spf_graph* graph = nullptr;
+  if (int s = spf_graph_create(&d, &graph); s != SPF_OK) {
     tableFailure("spf_graph_create", s);
   }
+  graph_.reset(graph);
   Counters::add("decision.route_table_graph_us", usSince(tp));
-  auto cleanup = [&](const char* what, int st) {
-    spf_route_table_destroy(table_);
-    spf_query_destroy(query_);
-    spf_graph_destroy(graph_);
-    table_ = nullptr;
-    query_ = nullptr;
-    graph_ = nullptr;
-    tableFailure(what, st);
-  };
-  try {
-    tp = std::chrono::steady_clock::now();
-    std::vector<uint32_t> src(d.num_nodes);
-    for (uint32_t i = 0; i < d.num_nodes; ++i) {
-      src[i] = i;
-    }
-    spf_query_desc qd{};
-    qd.num_queries = d.num_nodes;
-    qd.sources = src.data();
-    qd.flags = SPF_F_NEXTHOPS;
-    int s = SPF_OK;
-    if ((s = spf_query_create(graph_, &qd, &query_)) != SPF_OK) {
-      cleanup("spf_query_create", s);
-    }
-    if ((s = spf_query_run(query_)) != SPF_OK) {
-      cleanup("spf_query_run", s);
-    }
-    Counters::add("decision.route_table_query_us", usSince(tp));
-    tp = std::chrono::steady_clock::now();
-    // eligible prefixes (Decision.cpp:313-412 restricted to selectEcmpOpenr,
-    // and with bgpColumns selectEcmpBgp)
-    std::vector<uint32_t> annOff{0}, ann;
-    {
-      // eligibility and announcers per prefix on the host pool (read-only
-      // PrefixState lookups), kept in the map's iteration order
-      std::vector<std::pair<const thrift::IpPrefix*, const thrift::PrefixEntries*>> items;
-      items.reserve(ps.prefixes().size());
-      for (const auto& [prefix, entries] : ps.prefixes()) {
-        items.emplace_back(&prefix, &entries);
-      }
-      std::vector<uint8_t> keep(items.size(), 0);
-      std::vector<std::vector<Announcer>> anns(items.size());
-      std::vector<std::optional<BgpSel>> sels(items.size());
-      std::vector<std::optional<SelCol>> selCols(items.size());
-      // BGP candidates: every in-graph announcer (the selection assumes each
-      // is reachable from every node; checked below)
-      std::vector<std::vector<uint32_t>> bgpAll(items.size());
-      parallelFor(items.size(), hostThreads(items.size(), 256), [&](size_t i, unsigned) {
-        const auto& prefix = *items[i].first;
-        const auto& entries = *items[i].second;
-        bool otherArea = false, bgp = false, nonBgp = false, missingMv = false, inArea = false,
-             borderAnn = false;
-        for (const auto& [node, byArea] : entries) {
-          for (const auto& [area, entry] : byArea) {
-            otherArea |= area != area_;
-            inArea |= area == area_;
-            borderAnn |= area == area_ && borderNodes && borderNodes->count(node);
-            const bool isBgp = entry.type == thrift::PrefixType::BGP;
-            bgp |= isBgp;
-            nonBgp |= !isBgp;
-            missingMv |= isBgp && !entry.mv.has_value();
-          }
-        }
-        if ((bgp && !bgpColumns) || (bgp && (nonBgp || missingMv)) || entries.empty() ||
-            (otherArea && !borderNodes) || !inArea || borderAnn) {
-          return;
-        }
-        if (prefix.prefixAddress.addr.size() == 4 && !enableV4_) {
-          return;
-        }
-        if (getPrefixForwardingType(entries) != thrift::PrefixForwardingType::IP ||
-            getPrefixForwardingAlgorithm(entries) != thrift::PrefixForwardingAlgorithm::SP_ECMP) {
-          return;
-        }
-        if (!bgp) {
-          for (const auto& [node, byArea] : entries) {
-            auto it = ids_.find(node);
-            auto ea = byArea.find(area_);
-            if (it == ids_.end() || ea == byArea.end()) {
-              continue; // not in the graph / announced in another area: never reachable
-            }
-            anns[i].push_back(Announcer{it->second, ea->second});
-          }
-          keep[i] = 1;
-          return;
-        }
-        if (otherArea) {
-          return; // (interior-node tables of several areas: BGP stays on the host)
-        }
-        namespace mvu = MetricVectorUtils;
-        if (bgpUseIgpMetric) {
-          // a selected column: the fold runs per node on the device
-          // (spf_route_select_kernel).  Candidates = in-graph announcers in
-          // fold order, without those that advertise OPENR_IGP_COST
-          // (Decision.cpp:735-744: skipped before bestIgpMetric sees them)
-          SelCol sc;
-          std::vector<const thrift::MetricVector*> mvs;
-          const bool isV4 = prefix.prefixAddress.addr.size() == 4;
-          for (const auto& [node, byArea] : entries) {
-            for (const auto& [area, entry] : byArea) {
-              auto it = ids_.find(node);
-              if (it == ids_.end()) {
-                continue; // not in the graph: unreachable from every node
-              }
-              const thrift::MetricVector& mv = entry.mv.value();
-              if (mvu::getMetricEntityByType(mv, mvu::kOpenrIgpCostType)) {
-                continue;
-              }
-              for (const auto& me : mv.metrics) {
-                if (me.priority == mvu::kOpenrIgpCostPriority) {
-                  return; // std::sort leaves its order against the IGP entity open: host
-                }
-              }
-              anns[i].push_back(Announcer{it->second, entry});
-              mvs.push_back(&mv);
-              auto vias = ps.getLoopbackVias({node}, isV4, std::nullopt);
-              sc.via.push_back(vias.size() == 1 ? std::optional<thrift::NextHopThrift>(vias[0])
-                                                : std::nullopt);
-            }
-          }
-          if (mvs.size() > 32) {
-            anns[i].clear();
-            return; // the winners word has 32 bits: host
-          }
-          for (size_t c = 1; c < mvs.size(); ++c) {
-            for (size_t b = 0; b < c; ++b) {
-              const auto codes = mvu::bgpIgpPairCodes(*mvs[c], *mvs[b]);
-              sc.pair.push_back((uint16_t)((unsigned)codes[0] | ((unsigned)codes[1] << 3) |
-                                           ((unsigned)codes[2] << 6)));
-            }
-          }
-          selCols[i] = std::move(sc);
-          keep[i] = 3;
-          return;
-        }
-        // runBestPathSelectionBgp (Decision.cpp:714-803) without the IGP
-        // cost, every in-graph announcer reachable: entries in map order
-        std::optional<thrift::MetricVector> bestVector;
-        std::set<std::string> winners;
-        std::string bestNode, bestArea;
-        for (const auto& [node, byArea] : entries) {
-          for (const auto& [area, entry] : byArea) {
-            auto it = ids_.find(node);
-            if (it == ids_.end()) {
-              continue; // not in the graph: unreachable from every node
-            }
-            bgpAll[i].push_back(it->second);
-            const thrift::MetricVector& mvIn = entry.mv.value();
-            if (mvu::getMetricEntityByType(mvIn, mvu::kOpenrIgpCostType)) {
-              continue;
-            }
-            thrift::MetricVector mv = mvIn;
-            mvu::CompareResult cmp = mvu::CompareResult::WINNER;
-            if (bestVector) {
-              cmp = mvu::compareMetricVectors(mv, *bestVector);
-            }
-            switch (cmp) {
-            case mvu::CompareResult::WINNER:
-              winners.clear();
-              [[fallthrough]];
-            case mvu::CompareResult::TIE_WINNER:
-              bestVector = std::move(mv);
-              bestNode = node;
-              bestArea = area;
-              [[fallthrough]];
-            case mvu::CompareResult::TIE_LOOSER:
-              winners.insert(node);
-              break;
-            case mvu::CompareResult::TIE:
-            case mvu::CompareResult::ERROR:
-              // cannot order: no route at any node
-              sels[i] = BgpSel{};
-              keep[i] = 2;
-              return;
-            default:
-              break;
-            }
-          }
-        }
-        BgpSel sel;
-        if (!winners.empty()) {
-          // maybeFilterDrainedNodes (Decision.cpp:651-666)
-          std::set<std::string> undrained;
-          for (const auto& w : winners) {
-            if (!ls.isNodeOverloaded(w)) {
-              undrained.insert(w);
-            }
-          }
-          const auto& use = undrained.empty() ? winners : undrained;
-          auto vias = ps.getLoopbackVias({bestNode}, prefix.prefixAddress.addr.size() == 4,
-                                         std::nullopt);
-          if (vias.size() == 1) {
-            sel.bestEntry = entries.at(bestNode).at(bestArea);
-            sel.bestArea = bestArea;
-            sel.bestNexthop = vias.at(0);
-            for (const auto& w : use) {
-              anns[i].push_back(Announcer{ids_.at(w), entries.at(w).at(area_)});
-            }
-          }
-        }
-        sels[i] = std::move(sel);
-        keep[i] = 2;
-      }, 64);
-      // BGP columns need every in-graph announcer reachable from every node:
-      // reachability is symmetric here (links are up in both directions and a
-      // path's interior nodes are the same either way), so the announcer's
-      // own row answers for every node
-      std::unordered_map<uint32_t, bool> reachesAll;
-      std::vector<uint32_t> rowBuf(d.num_nodes);
-      for (size_t i = 0; i < items.size(); ++i) {
-        if (keep[i] != 2) {
-          continue;
-        }
-        for (const uint32_t a : bgpAll[i]) {
-          auto it = reachesAll.find(a);
-          if (it == reachesAll.end()) {
-            if (int st = spf_query_fetch_rows(query_, a, 1, rowBuf.data(), (size_t)d.num_nodes * 4,
-                                              0);
-                st != SPF_OK) {
-              cleanup("spf_query_fetch_rows", st);
-            }
-            const bool all = std::all_of(rowBuf.begin(), rowBuf.end(),
-                                         [](uint32_t x) { return x != 0xFFFFFFFFu; });
-            it = reachesAll.emplace(a, all).first;
-          }
-          if (!it->second) {
-            keep[i] = 0; // some node does not reach this announcer: the host path
-            break;
-          }
-        }
-      }
-      for (size_t i = 0; i < items.size(); ++i) {
-        if (keep[i]) {
-          prefixes_.push_back(*items[i].first);
-          announcers_.push_back(std::move(anns[i]));
-          bgp_.push_back(keep[i] == 2 ? std::move(sels[i]) : std::nullopt);
-          sel_.push_back(std::move(selCols[i]));
-          nbgp_ += keep[i] >= 2;
-        }
-      }
-    }
-    // prefix order: by first announcer id, so neighbouring lanes of the
-    // kernel read neighbouring distance / next-hop mask words of a row
-    {
-      std::vector<uint32_t> order(prefixes_.size());
-      for (uint32_t i = 0; i < order.size(); ++i) {
-        order[i] = i;
-      }
-      auto key = [&](uint32_t i) {
-        return announcers_[i].empty() ? 0xFFFFFFFFu : announcers_[i][0].id;
-      };
-      std::stable_sort(order.begin(), order.end(),
-                       [&](uint32_t x, uint32_t y) { return key(x) < key(y); });
-      std::vector<thrift::IpPrefix> px;
-      std::vector<std::vector<Announcer>> ax;
-      std::vector<std::optional<BgpSel>> bx;
-      std::vector<std::optional<SelCol>> sx;
-      sx.reserve(order.size());
-      px.reserve(order.size());
-      ax.reserve(order.size());
-      bx.reserve(order.size());
-      for (uint32_t i : order) {
-        px.push_back(std::move(prefixes_[i]));
-        ax.push_back(std::move(announcers_[i]));
-        bx.push_back(std::move(bgp_[i]));
-        sx.push_back(std::move(sel_[i]));
-      }
-      sel_ = std::move(sx);
-      prefixes_ = std::move(px);
-      announcers_ = std::move(ax);
-      bgp_ = std::move(bx);
-      for (const auto& as : announcers_) {
-        for (const auto& a : as) {
-          ann.push_back(a.id);
-        }
-        annOff.push_back((uint32_t)ann.size());
-      }
-    }
-    Counters::add("decision.route_table_prefixes_us", usSince(tp));
-    // node-label columns (Decision.cpp:415-481): one pseudo-prefix per (valid
-    // label, owner in the graph), owners of a label by name; the cell of node
-    // s is getNextHopsWithMetric(s, {owner}) with LFA off
-    {
-      // (label, owner id) sorted: labels ascending, owners by name (ids are
-      // name ranks) -- the order of a label -> sorted names map, without one
-      std::vector<std::pair<int32_t, uint32_t>> lab;
-      lab.reserve(names_.size());
-      nodeLabel_.assign(names_.size(), 0);
-      for (const auto& [node, db] : ls.getAdjacencyDatabases()) {
-        if (db.nodeLabel == 0 || !isMplsLabelValid(db.nodeLabel)) {
-          continue;
-        }
-        auto it = ids_.find(node);
-        if (it != ids_.end()) {
-          lab.emplace_back(db.nodeLabel, it->second);
-          nodeLabel_[it->second] = db.nodeLabel;
-        }
-      }
-      std::sort(lab.begin(), lab.end());
-      for (size_t i = 0; i < lab.size();) {
-        auto& cols =
-            labelCols_.emplace_hint(labelCols_.end(), lab[i].first, std::vector<uint32_t>{})
-                ->second;
-        size_t j = i;
-        for (; j < lab.size() && lab[j].first == lab[i].first; ++j) {
-          cols.push_back((uint32_t)(prefixes_.size() + owners_.size()));
-          owners_.push_back(LabelOwner{lab[j].first, lab[j].second});
-          ann.push_back(lab[j].second);
-          annOff.push_back((uint32_t)ann.size());
-        }
-        i = j;
-      }
-    }
-    Counters::add("decision.route_table_labels_us", usSince(tp));
-    // adjacency labels of every node (Decision.cpp:511-534), values copied
-    // (independent per node: read-only LinkState lookups on the host pool)
-    adjLabels_.resize(names_.size());
-    parallelFor(names_.size(), hostThreads(names_.size(), 256), [&](size_t i, unsigned) {
-      for (const auto& link : ls.linksFromNode(names_[i])) {
-        const int32_t label = link->getAdjLabelFromNode(names_[i]);
-        if (label == 0 || !isMplsLabelValid(label)) {
-          continue;
-        }
-        adjLabels_[i].push_back(AdjLabel{
-            label, link->getNhV6FromNode(names_[i]), link->getIfaceFromNode(names_[i]),
-            (int32_t)link->getMetricFromNode(names_[i]), link->getArea()});
-      }
-    }, 64);
-    Counters::add("decision.route_table_host_us", usSince(tp));
-    tp = std::chrono::steady_clock::now();
-    // selected columns: pair tables and loopback bits parallel to ann
-    std::vector<uint32_t> selColumns;
-    std::vector<uint64_t> pairOff{0};
-    std::vector<uint16_t> pairCodes;
-    std::vector<uint8_t> candFlags(ann.size(), 0);
-    for (size_t p = 0; p < prefixes_.size(); ++p) {
-      if (!sel_[p]) {
-        continue;
-      }
-      selColumns.push_back((uint32_t)p);
-      pairCodes.insert(pairCodes.end(), sel_[p]->pair.begin(), sel_[p]->pair.end());
-      pairOff.push_back(pairCodes.size());
-      for (size_t c = 0; c < sel_[p]->via.size(); ++c) {
-        candFlags[annOff[p] + c] = sel_[p]->via[c] ? 1 : 0;
-      }
-    }
-    nsel_ = selColumns.size();
-    spf_route_select_desc sd{};
-    sd.num_selected = (uint32_t)selColumns.size();
-    sd.columns = selColumns.data();
-    sd.pair_offsets = pairOff.data();
-    sd.pair_codes = pairCodes.data();
-    sd.cand_flags = candFlags.data();
-    if ((s = spf_route_table_create_sel(
-             query_, (uint32_t)(prefixes_.size() + owners_.size()), annOff.data(),
-             ann.empty() ? nullptr : ann.data(), lfa_ ? SPF_RT_LFA : 0u, nsel_ ? &sd : nullptr,
-             &table_)) != SPF_OK) {
-      cleanup("spf_route_table_create", s);
-    }
-    Counters::add("decision.route_table_create_us", usSince(tp));
-    tp = std::chrono::steady_clock::now();
-    if ((s = spf_route_table_run(table_)) != SPF_OK) {
-      cleanup("spf_route_table_run", s);
-    }
-    if ((s = spf_query_elapsed_ms(query_, &spfMs_)) != SPF_OK ||
-        (s = spf_route_table_elapsed_ms(table_, &routeMs_)) != SPF_OK ||
-        (s = spf_route_table_select_elapsed_ms(table_, &selectMs_)) != SPF_OK) {
-      cleanup("elapsed", s);
-    }
-  } catch (...) {
-    // (cleanup already released the handles when it threw)
-    spf_route_table_destroy(table_);
-    spf_query_destroy(query_);
-    spf_graph_destroy(graph_);
-    table_ = nullptr;
-    query_ = nullptr;
-    graph_ = nullptr;
-    throw;
+  tp = std::chrono::steady_clock::now();
+  std::vector<uint32_t> src(d.num_nodes);
+  for (uint32_t i = 0; i < d.num_nodes; ++i) {
+    src[i] = i;
   }
-  Counters::add("decision.route_table_run_us", usSince(tp));
+  spf_query_desc qd{};
+  qd.num_queries = d.num_nodes;
+  qd.sources = src.data();
+  qd.flags = SPF_F_NEXTHOPS;
+  int s = SPF_OK;
+  spf_query* query = nullptr;
+  if ((s = spf_query_create(graph_.get(), &qd, &query)) != SPF_OK) {
+    tableFailure("spf_query_create", s);
+  }
+  query_.reset(query);
+  if ((s = spf_query_run(query_.get())) != SPF_OK) {
+    tableFailure("spf_query_run", s);
+  }
+  Counters::add("decision.route_table_query_us", usSince(tp));
+  tp = std::chrono::steady_clock::now();
+  std::vector<uint32_t> annOff{0}, ann;
+  {
+    // eligible prefixes with their announcers, kept in the map's iteration order
+    PrefixScan scan{ls, ps, borderNodes, bgpColumns, bgpUseIgpMetric};
+    scan.items.reserve(ps.prefixes().size());
+    for (const auto& [prefix, entries] : ps.prefixes()) {
+      scan.items.emplace_back(&prefix, &entries);
+    }
+    const size_t n = scan.items.size();
+    scan.keep.assign(n, 0);
+    scan.anns.resize(n);
+    scan.sels.resize(n);
+    scan.selCols.resize(n);
+    scan.bgpAll.resize(n);
+    parallelFor(n, hostThreads(n, 256), [&](size_t i, unsigned) { scanPrefix(scan, i); }, 64);
+    dropUnreachableBgp(scan);
+    for (size_t i = 0; i < n; ++i) {
+      if (scan.keep[i]) {
+        prefixes_.push_back(*scan.items[i].first);
+        announcers_.push_back(std::move(scan.anns[i]));
+        bgp_.push_back(scan.keep[i] == 2 ? std::move(scan.sels[i]) : std::nullopt);
+        sel_.push_back(std::move(scan.selCols[i]));
+        nbgp_ += scan.keep[i] >= 2;
+      }
+    }
+  }
+  orderColumns(annOff, ann);
+  Counters::add("decision.route_table_prefixes_us", usSince(tp));
+  addNodeLabelColumns(ls, annOff, ann);
+  Counters::add("decision.route_table_labels_us", usSince(tp));
+  collectAdjLabels(ls);
+  Counters::add("decision.route_table_host_us", usSince(tp)); // (from the same start)
+  createAndRunTable(annOff, ann);
   Counters::add("decision.route_table_builds", 1);
 }
 
 AllNodesRouteTable::~AllNodesRouteTable() {
   const auto tp = std::chrono::steady_clock::now();
-  spf_route_table_destroy(table_);
-  spf_query_destroy(query_);
-  spf_graph_destroy(graph_);
+  table_.reset();
+  query_.reset();
+  graph_.reset();
   Counters::add("decision.route_table_destroy_us", usSince(tp));
 }
 
@@ -460,9 +486,9 @@ uint64_t AllNodesRouteTable::countRoutes() const {
   std::vector<uint32_t> metric(C), best(C);
   std::vector<uint64_t> links;
   for (uint32_t i = 0; i < names_.size(); ++i) {
-    const int w = spf_route_table_link_words(table_, i);
+    const int w = spf_route_table_link_words(table_.get(), i);
     links.resize(std::max<size_t>(1, C * (size_t)std::max(w, 0)));
-    if (int s = spf_route_table_fetch(table_, i, metric.data(), best.data(), links.data());
+    if (int s = spf_route_table_fetch(table_.get(), i, metric.data(), best.data(), links.data());
         s != SPF_OK) {
       tableFailure("spf_route_table_fetch", s);
     }
@@ -475,7 +501,7 @@ uint64_t AllNodesRouteTable::countRoutes() const {
 
 AllNodesRouteTable::Row AllNodesRouteTable::fetchRow(uint32_t i) const {
   Row r;
-  const int w = spf_route_table_link_words(table_, i);
+  const int w = spf_route_table_link_words(table_.get(), i);
   if (w < 0) {
     tableFailure("spf_route_table_link_words", w);
   }
@@ -487,43 +513,45 @@ AllNodesRouteTable::Row AllNodesRouteTable::fetchRow(uint32_t i) const {
   if (nsel_) {
     r.igp.resize(P);
     std::vector<uint32_t> winners(P);
-    if (int s = spf_route_table_fetch_sel(table_, i, r.metric.data(), r.best.data(),
+    if (int s = spf_route_table_fetch_sel(table_.get(), i, r.metric.data(), r.best.data(),
                                           r.links.data(), r.igp.data(), winners.data());
         s != SPF_OK) {
       tableFailure("spf_route_table_fetch_sel", s);
     }
-  } else if (int s =
-                 spf_route_table_fetch(table_, i, r.metric.data(), r.best.data(), r.links.data());
+  } else if (int s = spf_route_table_fetch(table_.get(), i, r.metric.data(), r.best.data(),
+                                           r.links.data());
              s != SPF_OK) {
     tableFailure("spf_route_table_fetch", s);
   }
   if (lfa_) {
     r.deg = row_[i + 1] - row_[i];
     r.lmet.resize(std::max<size_t>(1, P * r.deg));
-    if (int s = spf_route_table_fetch_link_metrics(table_, i, r.lmet.data()); s != SPF_OK) {
+    if (int s = spf_route_table_fetch_link_metrics(table_.get(), i, r.lmet.data()); s != SPF_OK) {
       tableFailure("spf_route_table_fetch_link_metrics", s);
     }
   }
   return r;
 }
 
+template <class Make>
+std::unordered_set<thrift::NextHopThrift> AllNodesRouteTable::cellNextHops(
+    uint32_t i, const Row& r, size_t p, Make&& make) const {
+  std::unordered_set<thrift::NextHopThrift> nhs;
+  const uint32_t e0 = row_[i];
+  forEachSetBit(r.W ? r.linksOf(p) : nullptr, r.W, [&](size_t j) {
+    nhs.insert(make(*halfLink_[e0 + j], (int32_t)r.linkMetric(p, (uint32_t)j)));
+  });
+  return nhs;
+}
+
 RibUnicastEntry AllNodesRouteTable::materialise(
     const std::string& node, uint32_t i, const Row& r, size_t p) const {
   const bool isV4 = prefixes_[p].prefixAddress.addr.size() == 4;
-  const uint32_t e0 = row_[i];
-  std::unordered_set<thrift::NextHopThrift> nhs;
-  const uint64_t* mask = r.W ? r.linksOf(p) : nullptr;
-  for (size_t k = 0; k < r.W; ++k) {
-    uint64_t m = mask[k];
-    while (m) {
-      const uint32_t j = (uint32_t)(k * 64 + __builtin_ctzll(m));
-      m &= m - 1;
-      const Link& l = *halfLink_[e0 + j];
-      nhs.insert(createNextHop(
-          isV4 ? l.getNhV4FromNode(node) : l.getNhV6FromNode(node), l.getIfaceFromNode(node),
-          (int32_t)r.linkMetric(p, j), std::nullopt, false, l.getArea()));
-    }
-  }
+  auto nhs = cellNextHops(i, r, p, [&](const Link& l, int32_t metric) {
+    return createNextHop(
+        isV4 ? l.getNhV4FromNode(node) : l.getNhV6FromNode(node), l.getIfaceFromNode(node),
+        metric, std::nullopt, false, l.getArea());
+  });
   if (sel_[p]) {
     // selectEcmpBgp (Decision.cpp:805-866) per node: the cell's best
     // candidate, its loopback with the cell's igp as metric
@@ -595,25 +623,15 @@ std::optional<RibMplsEntry> AllNodesRouteTable::nodeLabelEntry(
     }
     const std::string& node = names_[i];
     const std::string& owner = names_[o.id];
-    const uint32_t e0 = row_[i];
-    std::unordered_set<thrift::NextHopThrift> nhs;
-    const uint64_t* mask = r.W ? r.linksOf(col) : nullptr;
-    for (size_t k = 0; k < r.W; ++k) {
-      uint64_t m = mask[k];
-      while (m) {
-        const uint32_t j = (uint32_t)(k * 64 + __builtin_ctzll(m));
-        m &= m - 1;
-        const Link& l = *halfLink_[e0 + j];
-        const bool php = l.getOtherNodeName(node) == owner;
-        nhs.insert(createNextHop(
-            l.getNhV6FromNode(node), l.getIfaceFromNode(node), (int32_t)r.linkMetric(col, j),
-            createMplsAction(
-                php ? thrift::MplsActionCode::PHP : thrift::MplsActionCode::SWAP,
-                php ? std::nullopt : std::optional<int32_t>(label)),
-            false, l.getArea()));
-      }
-    }
-    return RibMplsEntry(label, std::move(nhs));
+    return RibMplsEntry(label, cellNextHops(i, r, col, [&](const Link& l, int32_t metric) {
+      const bool php = l.getOtherNodeName(node) == owner;
+      return createNextHop(
+          l.getNhV6FromNode(node), l.getIfaceFromNode(node), metric,
+          createMplsAction(
+              php ? thrift::MplsActionCode::PHP : thrift::MplsActionCode::SWAP,
+              php ? std::nullopt : std::optional<int32_t>(label)),
+          false, l.getArea());
+    }));
   }
   return std::nullopt;
 }
@@ -685,7 +703,7 @@ std::vector<uint32_t> AllNodesRouteTable::diff(const AllNodesRouteTable& older) 
   }
   std::vector<uint32_t> changed(names_.size());
   const auto tp = std::chrono::steady_clock::now();
-  if (int s = spf_route_table_diff(older.table_, table_, changed.data()); s != SPF_OK) {
+  if (int s = spf_route_table_diff(older.table_.get(), table_.get(), changed.data()); s != SPF_OK) {
     if (s == SPF_E_UNSUPPORTED) {
       // same row offsets, other neighbours behind them (a link moved)
       return diffMapped(older);
@@ -837,7 +855,7 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
   m.dirty_ann = dirtyAnn.data();
   std::vector<uint32_t> changed(V);
   const auto tp = std::chrono::steady_clock::now();
-  if (int s = spf_route_table_diff_mapped(older.table_, table_, &m, changed.data());
+  if (int s = spf_route_table_diff_mapped(older.table_.get(), table_.get(), &m, changed.data());
       s != SPF_OK) {
     if (s == SPF_E_UNSUPPORTED) {
       throw std::invalid_argument(std::string("AllNodesRouteTable::diff: ") +
@@ -865,63 +883,31 @@ std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string
   }
   std::vector<uint64_t> bits((C + 63) / 64);
   if (C) {
-    if (int s = spf_route_table_changed(table_, it->second, bits.data()); s != SPF_OK) {
+    if (int s = spf_route_table_changed(table_.get(), it->second, bits.data()); s != SPF_OK) {
       tableFailure("spf_route_table_changed", s);
     }
   }
   uint32_t uni = 0, lab = 0;
-  for (size_t k = 0; k < bits.size(); ++k) {
-    uint64_t m = bits[k];
-    while (m) {
-      const size_t p = k * 64 + __builtin_ctzll(m);
-      m &= m - 1;
-      (p < P ? uni : lab) += 1;
-    }
-  }
+  forEachSetBit(bits.data(), bits.size(), [&](size_t p) { (p < P ? uni : lab) += 1; });
   if (!goneCols_.empty()) {
     // deleted columns of the older table
     std::vector<uint64_t> gbits((goneCols_.size() + 63) / 64);
-    if (int s = spf_route_table_changed_gone(table_, it->second, gbits.data()); s != SPF_OK) {
+    if (int s = spf_route_table_changed_gone(table_.get(), it->second, gbits.data());
+        s != SPF_OK) {
       tableFailure("spf_route_table_changed_gone", s);
     }
-    for (size_t k = 0; k < gbits.size(); ++k) {
-      uint64_t m = gbits[k];
-      while (m) {
-        const size_t g = k * 64 + __builtin_ctzll(m);
-        m &= m - 1;
-        (goneCols_[g] < older_->prefixes_.size() ? uni : lab) += 1;
-      }
-    }
+    forEachSetBit(gbits.data(), gbits.size(), [&](size_t g) {
+      (goneCols_[g] < older_->prefixes_.size() ? uni : lab) += 1;
+    });
   }
   return {uni, lab};
 }
 
-DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
-  DecisionRouteUpdate u;
-  auto it = ids_.find(node);
-  if (!diffed_) {
-    throw std::logic_error("AllNodesRouteTable::delta: no diff has run");
-  }
-  if (it == ids_.end()) {
-    return u;
-  }
-  const uint32_t i = it->second;
-  const size_t P = prefixes_.size(), C = P + owners_.size();
-  std::vector<uint64_t> bits((C + 63) / 64);
-  if (C) {
-    if (int s = spf_route_table_changed(table_, i, bits.data()); s != SPF_OK) {
-      tableFailure("spf_route_table_changed", s);
-    }
-  }
-  bool any = false;
-  for (uint64_t b : bits) {
-    any |= b != 0;
-  }
-  // the node's row in the older table (none: every route here is new)
+std::vector<int32_t> AllNodesRouteTable::labelCandidates(
+    uint32_t i, const uint32_t* cols, size_t n, const uint32_t* gone, size_t ng) const {
   const uint32_t ia = rowOf_[i];
   const bool hasOld = ia != SPF_MAP_NONE;
-  const size_t Pa = older_->prefixes_.size(), Ca = Pa + older_->owners_.size();
-  // MPLS candidates: labels of changed label columns + adjacency labels
+  const size_t P = prefixes_.size(), Pa = older_->prefixes_.size();
   std::set<int32_t> labels;
   for (const AdjLabel& a : adjLabels_[i]) {
     labels.insert(a.label);
@@ -939,55 +925,97 @@ DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
     if (hasOld && older_->nodeLabel_[ia]) {
       labels.insert(older_->nodeLabel_[ia]);
     }
-    // deleted columns: unicast prefixes go, labels join the candidates
-    if (!goneCols_.empty()) {
-      std::vector<uint64_t> gbits((goneCols_.size() + 63) / 64);
-      if (int s = spf_route_table_changed_gone(table_, i, gbits.data()); s != SPF_OK) {
-        tableFailure("spf_route_table_changed_gone", s);
-      }
-      for (size_t k = 0; k < gbits.size(); ++k) {
-        uint64_t m = gbits[k];
-        while (m) {
-          const uint32_t c = goneCols_[k * 64 + __builtin_ctzll(m)];
-          m &= m - 1;
-          if (c < Pa) {
-            u.unicastRoutesToDelete.push_back(older_->prefixes_[c]);
-          } else {
-            labels.insert(older_->owners_[c - Pa].label);
-          }
-        }
-      }
+  }
+  for (size_t k = 0; k < ng; ++k) {
+    const uint32_t c = goneCols_[gone[k]];
+    if (c >= Pa) {
+      labels.insert(older_->owners_[c - Pa].label);
     }
   }
-  if (!any && labels.empty()) {
+  for (size_t k = 0; k < n; ++k) {
+    if (cols[k] >= P) {
+      labels.insert(owners_[cols[k] - P].label);
+    }
+  }
+  return {labels.begin(), labels.end()};
+}
+
+void AllNodesRouteTable::unicastDelta(
+    uint32_t i, const Row& r, const uint32_t* cols, size_t n, const uint32_t* gone, size_t ng,
+    DecisionRouteUpdate& u) const {
+  const size_t P = prefixes_.size(), Pa = older_->prefixes_.size();
+  for (size_t k = 0; k < ng; ++k) {
+    const uint32_t c = goneCols_[gone[k]];
+    if (c < Pa) {
+      u.unicastRoutesToDelete.push_back(older_->prefixes_[c]);
+    }
+  }
+  for (size_t k = 0; k < n; ++k) {
+    const size_t p = cols[k];
+    if (p >= P) {
+      continue; // a label column: among the MPLS candidates
+    }
+    if (r.metricOf(p) == 0xFFFFFFFFu) {
+      u.unicastRoutesToDelete.push_back(prefixes_[p]);
+    } else {
+      u.unicastRoutesToUpdate.push_back(materialise(names_[i], i, r, p));
+    }
+  }
+}
+
+void AllNodesRouteTable::mplsDelta(
+    uint32_t i, const Row& r, uint32_t ia, const Row& o, const std::vector<int32_t>& labels,
+    DecisionRouteUpdate& u) const {
+  for (const int32_t label : labels) {
+    auto ne = mplsEntry(i, r, label);
+    auto oe = ia != SPF_MAP_NONE ? older_->mplsEntry(ia, o, label) : std::nullopt;
+    if (ne && (!oe || !(*oe == *ne))) {
+      u.mplsRoutesToUpdate.push_back(std::move(*ne));
+    } else if (!ne && oe) {
+      u.mplsRoutesToDelete.push_back(label);
+    }
+  }
+}
+
+DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
+  DecisionRouteUpdate u;
+  auto it = ids_.find(node);
+  if (!diffed_) {
+    throw std::logic_error("AllNodesRouteTable::delta: no diff has run");
+  }
+  if (it == ids_.end()) {
     return u;
   }
-  const Row r = C ? fetchRow(i) : Row{};
-  for (size_t k = 0; k < bits.size(); ++k) {
-    uint64_t m = bits[k];
-    while (m) {
-      const size_t p = k * 64 + __builtin_ctzll(m);
-      m &= m - 1;
-      if (p >= P) {
-        labels.insert(owners_[p - P].label);
-      } else if (r.metricOf(p) == 0xFFFFFFFFu) {
-        u.unicastRoutesToDelete.push_back(prefixes_[p]);
-      } else {
-        u.unicastRoutesToUpdate.push_back(materialise(node, i, r, p));
-      }
+  const uint32_t i = it->second;
+  const size_t C = prefixes_.size() + owners_.size();
+  // the bitmaps first: changed columns and, after a mapped diff, the set
+  // bits of the gone bitmap (deleted columns of the older table)
+  std::vector<uint32_t> cols, gone;
+  if (C) {
+    std::vector<uint64_t> bits((C + 63) / 64);
+    if (int s = spf_route_table_changed(table_.get(), i, bits.data()); s != SPF_OK) {
+      tableFailure("spf_route_table_changed", s);
     }
+    forEachSetBit(bits.data(), bits.size(), [&](size_t p) { cols.push_back((uint32_t)p); });
   }
-  if (!labels.empty()) {
-    const Row o = hasOld && Ca ? older_->fetchRow(ia) : Row{};
-    for (const int32_t label : labels) {
-      auto ne = mplsEntry(i, r, label);
-      auto oe = hasOld ? older_->mplsEntry(ia, o, label) : std::nullopt;
-      if (ne && (!oe || !(*oe == *ne))) {
-        u.mplsRoutesToUpdate.push_back(std::move(*ne));
-      } else if (!ne && oe) {
-        u.mplsRoutesToDelete.push_back(label);
-      }
+  if (mapped_ && !goneCols_.empty()) {
+    std::vector<uint64_t> gbits((goneCols_.size() + 63) / 64);
+    if (int s = spf_route_table_changed_gone(table_.get(), i, gbits.data()); s != SPF_OK) {
+      tableFailure("spf_route_table_changed_gone", s);
     }
+    forEachSetBit(gbits.data(), gbits.size(), [&](size_t g) { gone.push_back((uint32_t)g); });
+  }
+  const std::vector<int32_t> labels =
+      labelCandidates(i, cols.data(), cols.size(), gone.data(), gone.size());
+  // then whole rows, where something reads them: this node's, and for MPLS
+  // candidates its row in the older table (none: every route here is new)
+  const Row r = C && (!cols.empty() || !labels.empty()) ? fetchRow(i) : Row{};
+  unicastDelta(i, r, cols.data(), cols.size(), gone.data(), gone.size(), u);
+  if (!labels.empty()) {
+    const uint32_t ia = rowOf_[i];
+    const size_t Ca = older_->prefixes_.size() + older_->owners_.size();
+    const Row o = ia != SPF_MAP_NONE && Ca ? older_->fetchRow(ia) : Row{};
+    mplsDelta(i, r, ia, o, labels, u);
   }
   return u;
 }
@@ -1024,14 +1052,12 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
   };
   const auto t0 = Clock::now();
   const uint32_t V = (uint32_t)names_.size();
-  const size_t P = prefixes_.size();
-  const size_t Pa = older_->prefixes_.size();
   std::vector<DecisionRouteUpdate> out(V);
   DeltasStats st;
 
   // ---- the changed cells of every row, compacted on the device
   spf_route_delta_sizes z{};
-  if (int s = spf_route_table_delta_pack(table_, &z); s != SPF_OK) {
+  if (int s = spf_route_table_delta_pack(table_.get(), &z); s != SPF_OK) {
     tableFailure("spf_route_table_delta_pack", s);
   }
   const auto t1 = Clock::now();
@@ -1040,7 +1066,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
   std::vector<uint64_t> links(z.link_words);
   std::vector<uint32_t> lmet(z.link_metrics);
   if (int s = spf_route_table_delta_fetch(
-          table_, cellOff.data(), col.data(), metric.data(), best.data(), links.data(),
+          table_.get(), cellOff.data(), col.data(), metric.data(), best.data(), links.data(),
           lfa_ ? lmet.data() : nullptr, goneOff.data(), gone.data());
       s != SPF_OK) {
     tableFailure("spf_route_table_delta_fetch", s);
@@ -1064,37 +1090,11 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
   const unsigned threads = hostThreads(V, 64);
   parallelFor(V, threads, [&](size_t n, unsigned) {
     const uint32_t i = (uint32_t)n;
-    const uint32_t ia = rowOf_[i];
-    const bool hasOld = ia != SPF_MAP_NONE;
-    std::set<int32_t> labels;
-    for (const AdjLabel& a : adjLabels_[i]) {
-      labels.insert(a.label);
-    }
-    if (hasOld) {
-      for (const AdjLabel& a : older_->adjLabels_[ia]) {
-        labels.insert(a.label);
-      }
-    }
-    if (mapped_) {
-      if (nodeLabel_[i]) {
-        labels.insert(nodeLabel_[i]);
-      }
-      if (hasOld && older_->nodeLabel_[ia]) {
-        labels.insert(older_->nodeLabel_[ia]);
-      }
-      for (uint64_t k = goneOff[i]; k < goneOff[i + 1]; ++k) {
-        const uint32_t c = goneCols_[gone[k]];
-        if (c >= Pa) {
-          labels.insert(older_->owners_[c - Pa].label);
-        }
-      }
-    }
-    for (uint64_t k = cellOff[i]; k < cellOff[i + 1]; ++k) {
-      if (col[k] >= P) {
-        labels.insert(owners_[col[k] - P].label);
-      }
-    }
-    for (const int32_t label : labels) {
+    const bool hasOld = rowOf_[i] != SPF_MAP_NONE;
+    labelsOf[i] = labelCandidates(
+        i, col.data() + cellOff[i], (size_t)(cellOff[i + 1] - cellOff[i]), gone.data() + goneOff[i],
+        (size_t)(goneOff[i + 1] - goneOff[i]));
+    for (const int32_t label : labelsOf[i]) {
       if (auto lc = labelCols_.find(label); lc != labelCols_.end()) {
         colsN[i].insert(colsN[i].end(), lc->second.begin(), lc->second.end());
       }
@@ -1106,7 +1106,6 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
     }
     std::sort(colsN[i].begin(), colsN[i].end());
     std::sort(colsO[i].begin(), colsO[i].end());
-    labelsOf[i].assign(labels.begin(), labels.end());
   });
 
   // ---- one sparse read per table
@@ -1137,7 +1136,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
     c.links.resize(c.lwPos[V]);
     c.lmet.resize(c.lmPos[V]);
     if (int s = spf_route_table_fetch_cells(
-            t.table_, n, c.rows.data(), c.cols.data(), c.metric.data(), c.best.data(),
+            t.table_.get(), n, c.rows.data(), c.cols.data(), c.metric.data(), c.best.data(),
             c.links.data(), lfa_ ? c.lmet.data() : nullptr);
         s != SPF_OK) {
       tableFailure("spf_route_table_fetch_cells", s);
@@ -1172,28 +1171,13 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
     DecisionRouteUpdate& u = out[i];
     const uint32_t ia = rowOf_[i];
     const bool hasOld = ia != SPF_MAP_NONE;
-    for (uint64_t k = goneOff[i]; k < goneOff[i + 1]; ++k) {
-      const uint32_t c = goneCols_[gone[k]];
-      if (c < Pa) {
-        u.unicastRoutesToDelete.push_back(older_->prefixes_[c]);
-      }
-    }
     const uint64_t k0 = cellOff[i], k1 = cellOff[i + 1];
-    if (k1 > k0) {
-      const Row r = view(*this, i, col.data() + k0, metric.data() + k0, best.data() + k0,
-                         (size_t)(k1 - k0), links.data() + lwBase[i], lmet.data() + lmBase[i]);
-      for (uint64_t k = k0; k < k1; ++k) {
-        const size_t p = col[k];
-        if (p >= P) {
-          continue; // a label column: among the candidates above
-        }
-        if (metric[k] == 0xFFFFFFFFu) {
-          u.unicastRoutesToDelete.push_back(prefixes_[p]);
-        } else {
-          u.unicastRoutesToUpdate.push_back(materialise(names_[i], i, r, p));
-        }
-      }
-    }
+    const Row r = k1 > k0
+        ? view(*this, i, col.data() + k0, metric.data() + k0, best.data() + k0, (size_t)(k1 - k0),
+               links.data() + lwBase[i], lmet.data() + lmBase[i])
+        : Row{};
+    unicastDelta(i, r, col.data() + k0, (size_t)(k1 - k0), gone.data() + goneOff[i],
+                 (size_t)(goneOff[i + 1] - goneOff[i]), u);
     if (labelsOf[i].empty()) {
       return;
     }
@@ -1207,15 +1191,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
                 (size_t)(co.off[i + 1] - b0), co.links.data() + co.lwPos[i],
                 co.lmet.data() + co.lmPos[i]);
     }
-    for (const int32_t label : labelsOf[i]) {
-      auto ne = mplsEntry(i, rn, label);
-      auto oe = hasOld ? older_->mplsEntry(ia, ro, label) : std::nullopt;
-      if (ne && (!oe || !(*oe == *ne))) {
-        u.mplsRoutesToUpdate.push_back(std::move(*ne));
-      } else if (!ne && oe) {
-        u.mplsRoutesToDelete.push_back(label);
-      }
-    }
+    mplsDelta(i, rn, ia, ro, labelsOf[i], u);
   });
   const auto t4 = Clock::now();
 

@@ -199,11 +199,32 @@ class AllNodesRouteTable {
     }
   };
   Row fetchRow(uint32_t i) const;
+  // next hops of cell p of node i: make(link, metric) for every link of its mask
+  template <class Make>
+  std::unordered_set<thrift::NextHopThrift> cellNextHops(
+      uint32_t i, const Row& r, size_t p, Make&& make) const;
   RibUnicastEntry materialise(const std::string& node, uint32_t i, const Row& r, size_t p) const;
   // the MPLS entry of `label` at node i: the node-label winner, else the
   // first adjacency label of that value
   std::optional<RibMplsEntry> mplsEntry(uint32_t i, const Row& r, int32_t label) const;
   std::optional<RibMplsEntry> nodeLabelEntry(uint32_t i, const Row& r, int32_t label) const;
+  // The delta of one node from the last diff, shared by delta(node) and
+  // deltas().  `cols` are the node's changed columns, `gone` its set bits of
+  // the gone bitmap (indices into goneCols_).
+  // MPLS candidates: labels of changed and gone label columns, both tables'
+  // adjacency labels and, after a mapped diff, both node labels (ascending)
+  std::vector<int32_t> labelCandidates(
+      uint32_t i, const uint32_t* cols, size_t n, const uint32_t* gone, size_t ng) const;
+  // unicast deletes of gone columns, then updates / deletes of changed ones
+  // (`r` holds at least `cols`)
+  void unicastDelta(
+      uint32_t i, const Row& r, const uint32_t* cols, size_t n, const uint32_t* gone, size_t ng,
+      DecisionRouteUpdate& u) const;
+  // mplsEntry of every label here (row r) against `older_` (row o of its node
+  // ia; SPF_MAP_NONE: every entry is new)
+  void mplsDelta(
+      uint32_t i, const Row& r, uint32_t ia, const Row& o, const std::vector<int32_t>& labels,
+      DecisionRouteUpdate& u) const;
 
   struct Announcer {
     uint32_t id;
@@ -232,6 +253,32 @@ class AllNodesRouteTable {
     std::vector<std::optional<thrift::NextHopThrift>> via; // the candidate's one loopback via
   };
   std::vector<std::optional<SelCol>> sel_; // per prefix
+  // The constructor's steps, in call order.  PrefixScan: what the constructor
+  // was given and, per prefix of PrefixState in map order, what scanPrefix
+  // found (keep: 0 not served, 1 Open/R, 2 BGP selected on the host, 3 a
+  // selected column).
+  struct PrefixScan {
+    const LinkState& ls;
+    const PrefixState& ps;
+    const std::unordered_set<std::string>* borderNodes;
+    bool bgpColumns, bgpUseIgpMetric;
+    std::vector<std::pair<const thrift::IpPrefix*, const thrift::PrefixEntries*>> items;
+    std::vector<uint8_t> keep;
+    std::vector<std::vector<Announcer>> anns;
+    std::vector<std::optional<BgpSel>> sels;
+    std::vector<std::optional<SelCol>> selCols;
+    // BGP candidates: every in-graph announcer (the selection assumes each
+    // is reachable from every node; dropUnreachableBgp checks)
+    std::vector<std::vector<uint32_t>> bgpAll;
+  };
+  void scanPrefix(PrefixScan& s, size_t i) const;
+  void dropUnreachableBgp(PrefixScan& s) const;
+  // annOff / ann: the announcer lists of every column, as the engine takes them
+  void orderColumns(std::vector<uint32_t>& annOff, std::vector<uint32_t>& ann);
+  void addNodeLabelColumns(
+      const LinkState& ls, std::vector<uint32_t>& annOff, std::vector<uint32_t>& ann);
+  void collectAdjLabels(const LinkState& ls);
+  void createAndRunTable(const std::vector<uint32_t>& annOff, const std::vector<uint32_t>& ann);
   size_t nbgp_{0}, nsel_{0};
   bool bgpDryRun_{false};
   // node-label columns: column prefixes_.size() + k is owners_[k]
@@ -260,9 +307,19 @@ class AllNodesRouteTable {
   float diffCallMs_{0};
   mutable DeltasStats lastDeltas_;
   std::vector<uint32_t> diffMapped(const AllNodesRouteTable& older);
-  spf_graph* graph_{nullptr};
-  spf_query* query_{nullptr};
-  spf_route_table* table_{nullptr};
+  // engine handles, declared so that destruction runs table, query, graph
+  struct GraphDeleter {
+    void operator()(spf_graph* g) const { spf_graph_destroy(g); }
+  };
+  struct QueryDeleter {
+    void operator()(spf_query* q) const { spf_query_destroy(q); }
+  };
+  struct TableDeleter {
+    void operator()(spf_route_table* t) const { spf_route_table_destroy(t); }
+  };
+  std::unique_ptr<spf_graph, GraphDeleter> graph_;
+  std::unique_ptr<spf_query, QueryDeleter> query_;
+  std::unique_ptr<spf_route_table, TableDeleter> table_;
   float spfMs_{0}, routeMs_{0}, selectMs_{0};
   bool diffed_{false};
 };

@@ -46,6 +46,31 @@ py::dict routeDbToPy(const DecisionRouteDb& db) {
   return out;
 }
 
+// A DecisionRouteUpdate for Python: updated routes as routeDbToPy renders
+// them, deleted prefixes as prefixKey, deleted labels as ints.
+struct RouteUpdatePy {
+  py::object unicast, mpls;
+  py::list unicastDeleted, mplsDeleted;
+};
+RouteUpdatePy routeUpdateToPy(const DecisionRouteUpdate& u) {
+  DecisionRouteDb db;
+  for (const auto& e : u.unicastRoutesToUpdate) {
+    db.unicastEntries.emplace(e.prefix, e);
+  }
+  for (const auto& e : u.mplsRoutesToUpdate) {
+    db.mplsEntries.emplace(e.label, e);
+  }
+  const py::dict both = routeDbToPy(db);
+  RouteUpdatePy out{both["unicast"], both["mpls"], py::list(), py::list()};
+  for (const auto& p : u.unicastRoutesToDelete) {
+    out.unicastDeleted.append(prefixKey(p));
+  }
+  for (const int32_t l : u.mplsRoutesToDelete) {
+    out.mplsDeleted.append(l);
+  }
+  return out;
+}
+
 py::tuple linkKey(const Link& l) {
   const auto& n = l.orderedNames();
   return py::make_tuple(
@@ -476,18 +501,8 @@ PYBIND11_MODULE(_openr_spf, m) {
       })
       .def("delta_mpls", [](const AllNodesRouteTable& t, const std::string& node) {
         // (updated MPLS routes as mpls_routes() renders them, deleted labels)
-        const DecisionRouteUpdate u = t.delta(node);
-        DecisionRouteDb db;
-        for (const auto& e : u.mplsRoutesToUpdate) {
-          db.mplsEntries.emplace(e.label, e);
-        }
-        py::dict all = routeDbToPy(db);
-        py::object upd = all["mpls"];
-        py::list del;
-        for (int32_t l : u.mplsRoutesToDelete) {
-          del.append(l);
-        }
-        return py::make_tuple(upd, del);
+        const RouteUpdatePy u = routeUpdateToPy(t.delta(node));
+        return py::make_tuple(u.mpls, u.mplsDeleted);
       })
       .def("diff", &AllNodesRouteTable::diff, py::arg("older"), py::keep_alive<1, 2>())
       .def("node_name", &AllNodesRouteTable::nodeName)
@@ -496,43 +511,17 @@ PYBIND11_MODULE(_openr_spf, m) {
       .def("changed_split", &AllNodesRouteTable::changedSplit)
       .def("delta", [](const AllNodesRouteTable& t, const std::string& node) {
         // (updated unicast routes as routes() renders them, deleted prefixes)
-        const DecisionRouteUpdate u = t.delta(node);
-        DecisionRouteDb db;
-        for (const auto& e : u.unicastRoutesToUpdate) {
-          db.unicastEntries.emplace(e.prefix, e);
-        }
-        py::dict all = routeDbToPy(db);
-        py::object upd = all["unicast"];
-        py::list del;
-        for (const auto& p : u.unicastRoutesToDelete) {
-          del.append(prefixKey(p));
-        }
-        return py::make_tuple(upd, del);
+        const RouteUpdatePy u = routeUpdateToPy(t.delta(node));
+        return py::make_tuple(u.unicast, u.unicastDeleted);
       })
       .def("deltas", [](const AllNodesRouteTable& t) {
         // per node, in id order: (upd, dele, mpls_upd, mpls_dele), rendered
         // as delta() / delta_mpls() render theirs
         const std::vector<DecisionRouteUpdate> all = t.deltas();
         py::list out;
-        for (const DecisionRouteUpdate& u : all) {
-          DecisionRouteDb db;
-          for (const auto& e : u.unicastRoutesToUpdate) {
-            db.unicastEntries.emplace(e.prefix, e);
-          }
-          for (const auto& e : u.mplsRoutesToUpdate) {
-            db.mplsEntries.emplace(e.label, e);
-          }
-          py::dict both = routeDbToPy(db);
-          py::object upd = both["unicast"];
-          py::object mupd = both["mpls"];
-          py::list del, mdel;
-          for (const auto& p : u.unicastRoutesToDelete) {
-            del.append(prefixKey(p));
-          }
-          for (int32_t l : u.mplsRoutesToDelete) {
-            mdel.append(l);
-          }
-          out.append(py::make_tuple(upd, del, mupd, mdel));
+        for (const DecisionRouteUpdate& du : all) {
+          const RouteUpdatePy u = routeUpdateToPy(du);
+          out.append(py::make_tuple(u.unicast, u.unicastDeleted, u.mpls, u.mplsDeleted));
         }
         return out;
       })
@@ -732,27 +721,12 @@ PYBIND11_MODULE(_openr_spf, m) {
     return out;
   });
   m.def("getRouteDelta", [](const DecisionRouteDb& newDb, const DecisionRouteDb& oldDb) {
-    const DecisionRouteUpdate u = getRouteDelta(newDb, oldDb);
-    DecisionRouteDb upd;
-    for (const auto& e : u.unicastRoutesToUpdate) {
-      upd.unicastEntries.emplace(e.prefix, e);
-    }
-    for (const auto& e : u.mplsRoutesToUpdate) {
-      upd.mplsEntries.emplace(e.label, e);
-    }
-    py::dict all = routeDbToPy(upd);
-    py::list udel, mdel;
-    for (const auto& p : u.unicastRoutesToDelete) {
-      udel.append(prefixKey(p));
-    }
-    for (const auto l : u.mplsRoutesToDelete) {
-      mdel.append(py::int_(l));
-    }
+    const RouteUpdatePy u = routeUpdateToPy(getRouteDelta(newDb, oldDb));
     py::dict out;
-    out["unicastRoutesToUpdate"] = all["unicast"];
-    out["unicastRoutesToDelete"] = udel;
-    out["mplsRoutesToUpdate"] = all["mpls"];
-    out["mplsRoutesToDelete"] = mdel;
+    out["unicastRoutesToUpdate"] = u.unicast;
+    out["unicastRoutesToDelete"] = u.unicastDeleted;
+    out["mplsRoutesToUpdate"] = u.mpls;
+    out["mplsRoutesToDelete"] = u.mplsDeleted;
     return out;
   });
 

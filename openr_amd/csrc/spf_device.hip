@@ -46,6 +46,7 @@
 #include <map>
 #include <mutex>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "openr_spf.h"
@@ -9008,6 +9009,66 @@ int dev_upload(T** dst, const T* src, size_t n) {
   return SPF_OK;
 }
 
+// Move-only owner of a device array (hipMalloc / hipFree, not the query
+// pool): the pointer, read wherever a raw one is expected, and its capacity
+// in elements.  The array's device must be current when the owner goes.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) {
+      (void)hipFree(p);
+    }
+    p = nullptr;
+    cap = 0;
+  }
+  operator T*() const { return p; }
+  // grow-only, and contents are not kept (every user rewrites them)
+  hipError_t reserve(size_t n) {
+    if (n <= cap) {
+      return hipSuccess;
+    }
+    release();
+    T* q = nullptr;
+    const hipError_t e = hipMalloc((void**)&q, n * sizeof(T));
+    if (e == hipSuccess) {
+      p = q;
+      cap = n;
+    }
+    return e;
+  }
+  // the first n elements from the host (n = 0: nothing, the pointer stays null)
+  int upload(const T* src, size_t n) {
+    HIP_TRY(reserve(n));
+    HIP_TRY(n ? hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess);
+    return SPF_OK;
+  }
+};
+
+// Owner of one hipEvent_t (created on demand, destroyed with its owner).
+struct DevEvent {
+  hipEvent_t e = nullptr;
+  DevEvent() = default;
+  DevEvent(const DevEvent&) = delete;
+  DevEvent& operator=(const DevEvent&) = delete;
+  ~DevEvent() {
+    if (e) {
+      (void)hipEventDestroy(e);
+    }
+  }
+  hipError_t create() { return hipEventCreate(&e); }
+  operator hipEvent_t() const { return e; }
+};
+
 // The v2 next-hop pass's tables (spf_nh_levels_v2_kernel): every source with
 // at most kNsHeldMax mask words is a solo item or a member of a group of
 // sources with the same short distinct-neighbour list (<= kNlGN neighbours,
@@ -14508,51 +14569,46 @@ struct spf_route_table {
   spf_query* q = nullptr;
   uint32_t P = 0;
   std::vector<uint64_t> lk_off; // [nq + 1]
-  uint32_t *d_ann_off = nullptr, *d_ann = nullptr, *d_metric = nullptr, *d_best = nullptr;
-  uint64_t *d_lk_off = nullptr, *d_links = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBuf<uint32_t> d_ann_off, d_ann, d_metric, d_best;
+  DevBuf<uint64_t> d_lk_off, d_links;
+  DevEvent ev0, ev1;
   bool ran = false;
   // spf_route_table_diff against an older table: changed-cell bitmap
-  uint64_t* d_diff = nullptr;
-  uint32_t* d_count = nullptr;
+  DevBuf<uint64_t> d_diff;
+  DevBuf<uint32_t> d_count;
   // SPF_RT_LFA
   bool lfa = false;
   std::vector<uint64_t> lm_off; // [nq + 1] per-link metric offsets (P * deg)
-  uint64_t* d_lm_off = nullptr;
-  uint32_t* d_lmet = nullptr;
-  int32_t* d_row_of = nullptr;
+  DevBuf<uint64_t> d_lm_off;
+  DevBuf<uint32_t> d_lmet;
+  DevBuf<int32_t> d_row_of;
   // spf_route_table_diff_mapped: up links of every row's source, the staged
   // maps and the gone-column bitmap of the last mapped diff
   std::vector<uint32_t> deg; // [nq]
-  uint32_t* d_map = nullptr;
-  size_t map_cap = 0; // uint32 words
-  uint64_t* d_gone = nullptr;
-  size_t gone_cap = 0; // uint64 words
+  DevBuf<uint32_t> d_map;
+  DevBuf<uint64_t> d_gone;
   uint32_t gone_n = 0;
   bool mapped = false;
   // spf_route_table_delta_pack / _fetch_cells: `epoch` counts runs and diffs
   // (a pack is stale once it moved on); the packed list and the gather
-  // staging are grow-only buffers (capacities in elements)
+  // staging are grow-only (DevBuf::reserve)
   uint64_t epoch = 0, pk_epoch = 0;
   bool diffed = false, diff_mapped_last = false, packed = false;
   spf_route_delta_sizes pk{};
-  uint32_t *d_pk_cnt = nullptr, *d_pk_cell = nullptr, *d_pk_lmet = nullptr, *d_pk_gone = nullptr;
-  uint64_t *d_pk_off = nullptr, *d_pk_links = nullptr;
-  size_t pk_cell_cap = 0, pk_lmet_cap = 0, pk_gone_cap = 0, pk_links_cap = 0;
-  uint32_t *d_gc_idx = nullptr, *d_gc_out = nullptr, *d_gc_lmet = nullptr;
-  uint64_t *d_gc_pos = nullptr, *d_gc_links = nullptr;
-  size_t gc_idx_cap = 0, gc_out_cap = 0, gc_lmet_cap = 0, gc_pos_cap = 0, gc_links_cap = 0;
+  DevBuf<uint32_t> d_pk_cnt, d_pk_cell, d_pk_lmet, d_pk_gone;
+  DevBuf<uint64_t> d_pk_off, d_pk_links;
+  DevBuf<uint32_t> d_gc_idx, d_gc_out, d_gc_lmet;
+  DevBuf<uint64_t> d_gc_pos, d_gc_links;
   // selected columns (spf_route_table_create_sel): S of them, sel_col[k] the
   // column; per-cell winners / best / igp are [nq][S]; evs0 .. ev0 times the
   // selection kernel
   uint32_t S = 0;
   std::vector<uint32_t> sel_col;
-  uint32_t *d_sel_col = nullptr, *d_sel_of = nullptr, *d_sel_w = nullptr, *d_sel_best = nullptr,
-           *d_sel_igp = nullptr;
-  uint64_t* d_pair_off = nullptr;
-  uint16_t* d_pair = nullptr;
-  uint8_t* d_cflags = nullptr;
-  hipEvent_t evs0 = nullptr;
+  DevBuf<uint32_t> d_sel_col, d_sel_of, d_sel_w, d_sel_best, d_sel_igp;
+  DevBuf<uint64_t> d_pair_off;
+  DevBuf<uint16_t> d_pair;
+  DevBuf<uint8_t> d_cflags;
+  DevEvent evs0;
 };
 
 namespace {
@@ -14560,31 +14616,19 @@ void free_route_table(spf_route_table* t) {
   if (!t) {
     return;
   }
-  (void)hipSetDevice(t->q->g->device);
+  (void)hipSetDevice(t->q->g->device); // before delete: the DevBuf / DevEvent members free there
   t->q->live_tables.fetch_sub(1, std::memory_order_relaxed);
-  for (void* p : {(void*)t->d_ann_off, (void*)t->d_ann, (void*)t->d_metric, (void*)t->d_best,
-                  (void*)t->d_lk_off, (void*)t->d_links, (void*)t->d_diff, (void*)t->d_count,
-                  (void*)t->d_lm_off, (void*)t->d_lmet, (void*)t->d_row_of, (void*)t->d_map,
-                  (void*)t->d_gone, (void*)t->d_pk_cnt, (void*)t->d_pk_cell, (void*)t->d_pk_lmet,
-                  (void*)t->d_pk_gone, (void*)t->d_pk_off, (void*)t->d_pk_links,
-                  (void*)t->d_gc_idx, (void*)t->d_gc_out, (void*)t->d_gc_lmet, (void*)t->d_gc_pos,
-                  (void*)t->d_gc_links, (void*)t->d_sel_col, (void*)t->d_sel_of,
-                  (void*)t->d_sel_w, (void*)t->d_sel_best, (void*)t->d_sel_igp,
-                  (void*)t->d_pair_off, (void*)t->d_pair, (void*)t->d_cflags}) {
-    if (p) {
-      (void)hipFree(p);
+  delete t;
+}
+
+// ann_offsets [num_prefixes + 1] never decreases
+int check_ann_offsets_monotone(const uint32_t* ann_offsets, uint32_t num_prefixes) {
+  for (uint32_t p = 0; p < num_prefixes; ++p) {
+    if (ann_offsets[p + 1] < ann_offsets[p]) {
+      return fail(SPF_E_INVALID, "ann_offsets not monotone");
     }
   }
-  if (t->evs0) {
-    (void)hipEventDestroy(t->evs0);
-  }
-  if (t->ev0) {
-    (void)hipEventDestroy(t->ev0);
-  }
-  if (t->ev1) {
-    (void)hipEventDestroy(t->ev1);
-  }
-  delete t;
+  return SPF_OK;
 }
 } // namespace
 
@@ -14618,10 +14662,8 @@ int spf_route_table_create_ex(
   if (na && !announcers) {
     return fail(SPF_E_INVALID, "null announcers");
   }
-  for (uint32_t p = 0; p < num_prefixes; ++p) {
-    if (ann_offsets[p + 1] < ann_offsets[p]) {
-      return fail(SPF_E_INVALID, "ann_offsets not monotone");
-    }
+  if (int st = check_ann_offsets_monotone(ann_offsets, num_prefixes); st != SPF_OK) {
+    return st;
   }
   for (uint32_t i = 0; i < na; ++i) {
     if (announcers[i] >= g->V) {
@@ -14673,12 +14715,11 @@ int spf_route_table_create_ex(
   };
   if (lfa) {
     int s1 = SPF_OK;
-    if ((s1 = dev_upload(&t->d_row_of, row_of.data(), row_of.size())) ||
-        (s1 = dev_upload(&t->d_lm_off, t->lm_off.data(), t->lm_off.size()))) {
+    if ((s1 = t->d_row_of.upload(row_of.data(), row_of.size())) ||
+        (s1 = t->d_lm_off.upload(t->lm_off.data(), t->lm_off.size()))) {
       return bail(s1);
     }
-    if (t->lm_off.back() &&
-        hipMalloc((void**)&t->d_lmet, t->lm_off.back() * 4) != hipSuccess) {
+    if (t->d_lmet.reserve(t->lm_off.back()) != hipSuccess) {
       return bail(fail(SPF_E_NOMEM, "LFA link metrics"));
     }
   }
@@ -14688,20 +14729,16 @@ int spf_route_table_create_ex(
     off.assign(1, 0);
   }
   int st = SPF_OK;
-  if ((st = dev_upload(&t->d_ann_off, off.data(), off.size())) ||
-      (na && (st = dev_upload(&t->d_ann, announcers, na))) ||
-      (st = dev_upload(&t->d_lk_off, t->lk_off.data(), t->lk_off.size()))) {
+  if ((st = t->d_ann_off.upload(off.data(), off.size())) ||
+      (st = t->d_ann.upload(announcers, na)) ||
+      (st = t->d_lk_off.upload(t->lk_off.data(), t->lk_off.size()))) {
     return bail(st);
   }
-  if (cells) {
-    if (hipMalloc((void**)&t->d_metric, cells * 4) != hipSuccess ||
-        hipMalloc((void**)&t->d_best, cells * 4) != hipSuccess ||
-        (t->lk_off.back() &&
-         hipMalloc((void**)&t->d_links, t->lk_off.back() * 8) != hipSuccess)) {
-      return bail(fail(SPF_E_NOMEM, "route table allocation"));
-    }
+  if (t->d_metric.reserve(cells) != hipSuccess || t->d_best.reserve(cells) != hipSuccess ||
+      t->d_links.reserve(t->lk_off.back()) != hipSuccess) { // (no cells: no link words)
+    return bail(fail(SPF_E_NOMEM, "route table allocation"));
   }
-  if (hipEventCreate(&t->ev0) != hipSuccess || hipEventCreate(&t->ev1) != hipSuccess) {
+  if (t->ev0.create() != hipSuccess || t->ev1.create() != hipSuccess) {
     return bail(fail(SPF_E_DEVICE, "hipEventCreate"));
   }
   *out = t;
@@ -14726,11 +14763,9 @@ int spf_route_table_create_sel(
   if (sel->pair_offsets[0] != 0) {
     return fail(SPF_E_INVALID, "pair_offsets[0] != 0");
   }
-  // (create_ex checks ann_offsets again; these reads need it monotone first)
-  for (uint32_t p = 0; p < num_prefixes; ++p) {
-    if (ann_offsets[p + 1] < ann_offsets[p]) {
-      return fail(SPF_E_INVALID, "ann_offsets not monotone");
-    }
+  // (the reads below need it monotone, before create_ex looks)
+  if (int st = check_ann_offsets_monotone(ann_offsets, num_prefixes); st != SPF_OK) {
+    return st;
   }
   std::vector<uint32_t> sel_of(num_prefixes, kInf32);
   for (uint32_t k = 0; k < S; ++k) {
@@ -14766,20 +14801,18 @@ int spf_route_table_create_sel(
   const uint32_t na = ann_offsets[num_prefixes];
   const size_t cells = (size_t)q->nq * S;
   int st = SPF_OK;
-  if ((st = dev_upload(&t->d_sel_col, sel->columns, (size_t)S)) ||
-      (st = dev_upload(&t->d_sel_of, sel_of.data(), sel_of.size())) ||
-      (st = dev_upload(&t->d_pair_off, sel->pair_offsets, (size_t)S + 1)) ||
-      (st = dev_upload(&t->d_pair, sel->pair_codes, (size_t)npair)) ||
-      (st = dev_upload(&t->d_cflags, sel->cand_flags, (size_t)na))) {
+  if ((st = t->d_sel_col.upload(sel->columns, (size_t)S)) ||
+      (st = t->d_sel_of.upload(sel_of.data(), sel_of.size())) ||
+      (st = t->d_pair_off.upload(sel->pair_offsets, (size_t)S + 1)) ||
+      (st = t->d_pair.upload(sel->pair_codes, (size_t)npair)) ||
+      (st = t->d_cflags.upload(sel->cand_flags, (size_t)na))) {
     return bail(st);
   }
-  if (cells &&
-      (hipMalloc((void**)&t->d_sel_w, cells * 4) != hipSuccess ||
-       hipMalloc((void**)&t->d_sel_best, cells * 4) != hipSuccess ||
-       hipMalloc((void**)&t->d_sel_igp, cells * 4) != hipSuccess)) {
+  if (t->d_sel_w.reserve(cells) != hipSuccess || t->d_sel_best.reserve(cells) != hipSuccess ||
+      t->d_sel_igp.reserve(cells) != hipSuccess) {
     return bail(fail(SPF_E_NOMEM, "selection cells"));
   }
-  if (hipEventCreate(&t->evs0) != hipSuccess) {
+  if (t->evs0.create() != hipSuccess) {
     return bail(fail(SPF_E_DEVICE, "hipEventCreate"));
   }
   *out = t;
@@ -14984,15 +15017,54 @@ int spf_route_table_fetch_link_metrics(spf_route_table* t, uint32_t i, uint32_t*
 
 } // extern "C"
 
-extern "C" {
-
-int spf_route_table_diff(spf_route_table* older, spf_route_table* newer, uint32_t* changed) {
-  SPF_ABI_RANGE("spf_route_table_diff");
+namespace {
+// The frame of spf_route_table_diff and _diff_mapped: their own checks come
+// after diff_check_args, their launch between diff_begin and diff_finish.
+int diff_check_args(const spf_route_table* older, const spf_route_table* newer,
+                    const uint32_t* changed) {
   if (!older || !newer || (newer->q->nq && !changed)) {
     return fail(SPF_E_INVALID, "null argument");
   }
   if (!older->ran || !newer->ran) {
     return fail(SPF_E_INVALID, "both tables must have run");
+  }
+  return SPF_OK;
+}
+
+// the diff is accepted: state moves on; counts (zeroed) and bitmap exist, if there are rows
+int diff_begin(const spf_route_table* older, spf_route_table* newer, bool mapped) {
+  ++newer->epoch;
+  newer->diffed = true;
+  newer->diff_mapped_last = mapped;
+  const uint32_t nq = newer->q->nq, pw = (newer->P + 63) / 64;
+  if (nq == 0) {
+    return SPF_OK;
+  }
+  const spf_graph* gb = newer->q->g;
+  HIP_TRY(hipSetDevice(gb->device));
+  HIP_TRY(newer->d_count.reserve(nq));
+  HIP_TRY(newer->d_diff.reserve((size_t)nq * pw));
+  // the older table's rows are read on the newer table's stream
+  HIP_TRY(hipStreamSynchronize(older->q->g->stream));
+  HIP_TRY(hipMemsetAsync(newer->d_count, 0, (size_t)nq * 4, gb->stream));
+  return SPF_OK;
+}
+
+int diff_finish(spf_route_table* newer, uint32_t* changed) {
+  const spf_graph* gb = newer->q->g;
+  HIP_TRY(hipMemcpyAsync(changed, newer->d_count, (size_t)newer->q->nq * 4, hipMemcpyDeviceToHost,
+                         gb->stream));
+  HIP_TRY(hipStreamSynchronize(gb->stream));
+  return SPF_OK;
+}
+} // namespace
+
+extern "C" {
+
+int spf_route_table_diff(spf_route_table* older, spf_route_table* newer, uint32_t* changed) {
+  SPF_ABI_RANGE("spf_route_table_diff");
+  if (int st = diff_check_args(older, newer, changed); st != SPF_OK) {
+    return st;
   }
   const spf_graph* ga = older->q->g;
   const spf_graph* gb = newer->q->g;
@@ -15003,22 +15075,9 @@ int spf_route_table_diff(spf_route_table* older, spf_route_table* newer, uint32_
                 "tables differ in rows, prefixes or link layout (rematerialise instead)");
   }
   const uint32_t nq = newer->q->nq, P = newer->P, pw = (P + 63) / 64;
-  ++newer->epoch;
-  newer->diffed = true;
-  newer->diff_mapped_last = false;
-  if (nq == 0) {
-    return SPF_OK;
+  if (int st = diff_begin(older, newer, false); st != SPF_OK || nq == 0) {
+    return st;
   }
-  HIP_TRY(hipSetDevice(gb->device));
-  if (!newer->d_count) {
-    HIP_TRY(hipMalloc((void**)&newer->d_count, (size_t)nq * 4));
-    if (pw) {
-      HIP_TRY(hipMalloc((void**)&newer->d_diff, (size_t)nq * pw * 8));
-    }
-  }
-  // the older table's rows are read on the newer table's stream
-  HIP_TRY(hipStreamSynchronize(ga->stream));
-  HIP_TRY(hipMemsetAsync(newer->d_count, 0, (size_t)nq * 4, gb->stream));
   if (P) {
     const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)gb->num_cus * 8);
     SPF_LAUNCH(spf_route_table_diff_kernel, dim3(grid), dim3(256), 0, gb->stream,
@@ -15028,10 +15087,7 @@ int spf_route_table_diff(spf_route_table* older, spf_route_table* newer, uint32_
                        newer->d_lm_off);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(changed, newer->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost,
-                         gb->stream));
-  HIP_TRY(hipStreamSynchronize(gb->stream));
-  return SPF_OK;
+  return diff_finish(newer, changed);
 }
 
 int spf_route_table_changed(spf_route_table* t, uint32_t i, uint64_t* bits) {
@@ -15055,11 +15111,8 @@ int spf_route_table_diff_mapped(
     spf_route_table* older, spf_route_table* newer, const spf_route_diff_map* map,
     uint32_t* changed) {
   SPF_ABI_RANGE("spf_route_table_diff_mapped");
-  if (!older || !newer || (newer->q->nq && !changed)) {
-    return fail(SPF_E_INVALID, "null argument");
-  }
-  if (!older->ran || !newer->ran) {
-    return fail(SPF_E_INVALID, "both tables must have run");
+  if (int st = diff_check_args(older, newer, changed); st != SPF_OK) {
+    return st;
   }
   static const spf_route_diff_map kIdentity{};
   const spf_route_diff_map& m = map ? *map : kIdentity;
@@ -15186,11 +15239,8 @@ int spf_route_table_diff_mapped(
   }
   newer->gone_n = ng;
   newer->mapped = true;
-  ++newer->epoch;
-  newer->diffed = true;
-  newer->diff_mapped_last = true;
-  if (nq == 0) {
-    return SPF_OK;
+  if (int st = diff_begin(older, newer, true); st != SPF_OK || nq == 0) {
+    return st;
   }
   // ---- one staging buffer of uint32 words for every map the kernel reads
   std::vector<uint32_t> stage;
@@ -15209,36 +15259,10 @@ int spf_route_table_diff_mapped(
   const size_t o_lof = nlink ? put(m.link_of, nlink) : 0;
   const size_t o_doff = m.dirty_off ? put(m.dirty_off, (size_t)P + 1) : 0;
   const size_t o_dann = nd ? put(m.dirty_ann, nd) : 0;
-  HIP_TRY(hipSetDevice(gb->device));
-  if (!newer->d_count) {
-    HIP_TRY(hipMalloc((void**)&newer->d_count, (size_t)nq * 4));
-    if (pw) {
-      HIP_TRY(hipMalloc((void**)&newer->d_diff, (size_t)nq * pw * 8));
-    }
-  }
-  if (stage.size() > newer->map_cap) {
-    if (newer->d_map) {
-      (void)hipFree(newer->d_map);
-      newer->d_map = nullptr;
-      newer->map_cap = 0;
-    }
-    HIP_TRY(hipMalloc((void**)&newer->d_map, stage.size() * 4));
-    newer->map_cap = stage.size();
-  }
-  if ((size_t)nq * gw > newer->gone_cap) {
-    if (newer->d_gone) {
-      (void)hipFree(newer->d_gone);
-      newer->d_gone = nullptr;
-      newer->gone_cap = 0;
-    }
-    HIP_TRY(hipMalloc((void**)&newer->d_gone, (size_t)nq * gw * 8));
-    newer->gone_cap = (size_t)nq * gw;
-  }
-  // the older table's rows are read on the newer table's stream
-  HIP_TRY(hipStreamSynchronize(ga->stream));
+  HIP_TRY(newer->d_map.reserve(stage.size()));
+  HIP_TRY(newer->d_gone.reserve((size_t)nq * gw));
   HIP_TRY(hipMemcpyAsync(newer->d_map, stage.data(), stage.size() * 4, hipMemcpyHostToDevice,
                          gb->stream));
-  HIP_TRY(hipMemsetAsync(newer->d_count, 0, (size_t)nq * 4, gb->stream));
   if (P || ng) {
     RouteDiffMapArgs a{};
     const uint32_t* d = newer->d_map;
@@ -15278,10 +15302,7 @@ int spf_route_table_diff_mapped(
     SPF_LAUNCH(spf_route_table_diff_mapped_kernel, dim3(grid), dim3(256), 0, gb->stream, a);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(changed, newer->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost,
-                         gb->stream));
-  HIP_TRY(hipStreamSynchronize(gb->stream));
-  return SPF_OK;
+  return diff_finish(newer, changed);
 }
 
 int spf_route_table_changed_gone(spf_route_table* t, uint32_t i, uint64_t* bits) {
@@ -15306,26 +15327,6 @@ int spf_route_table_changed_gone(spf_route_table* t, uint32_t i, uint64_t* bits)
 
 } // extern "C"
 
-namespace {
-// grow-only device buffer of `n` elements (contents are not kept)
-template <class T>
-int grow_dev(T** p, size_t* cap, size_t n) {
-  if (n <= *cap) {
-    return SPF_OK;
-  }
-  if (*p) {
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-  }
-  if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess) {
-    return fail(SPF_E_NOMEM, "route delta buffer");
-  }
-  *cap = n;
-  return SPF_OK;
-}
-} // namespace
-
 extern "C" {
 
 int spf_route_table_delta_pack(spf_route_table* t, spf_route_delta_sizes* sizes) {
@@ -15344,11 +15345,9 @@ int spf_route_table_delta_pack(spf_route_table* t, spf_route_delta_sizes* sizes)
   t->pk = spf_route_delta_sizes{};
   if (nq && (pw || gw)) {
     HIP_TRY(hipSetDevice(g->device));
-    if (!t->d_pk_cnt) {
-      HIP_TRY(hipMalloc((void**)&t->d_pk_cnt, (size_t)nq * 2 * 4));
-      HIP_TRY(hipMalloc((void**)&t->d_pk_off, (4 * ((size_t)nq + 1) + 4) * 8));
-    }
-    const uint64_t* gone_bits = gw ? t->d_gone : nullptr;
+    HIP_TRY(t->d_pk_cnt.reserve((size_t)nq * 2));
+    HIP_TRY(t->d_pk_off.reserve(4 * ((size_t)nq + 1) + 4));
+    const uint64_t* gone_bits = gw ? t->d_gone.p : nullptr;
     const uint32_t waves = 256 / 64;
     const uint32_t cgrid =
         std::min<uint32_t>((nq + waves - 1) / waves, (uint32_t)g->num_cus * 8);
@@ -15356,7 +15355,7 @@ int spf_route_table_delta_pack(spf_route_table* t, spf_route_delta_sizes* sizes)
                gone_bits, nq, pw, gw, t->d_pk_cnt);
     HIP_TRY(hipGetLastError());
     SPF_LAUNCH(spf_route_delta_scan_kernel, dim3(1), dim3(kDeltaScanBlock), 0, g->stream,
-               t->d_pk_cnt, t->d_lk_off, t->lfa ? t->d_lm_off : nullptr, P, nq, t->d_pk_off);
+               t->d_pk_cnt, t->d_lk_off, t->lfa ? t->d_lm_off.p : nullptr, P, nq, t->d_pk_off);
     HIP_TRY(hipGetLastError());
     uint64_t tot[4];
     HIP_TRY(hipMemcpyAsync(tot, t->d_pk_off + 4 * ((size_t)nq + 1), sizeof(tot),
@@ -15367,12 +15366,11 @@ int spf_route_table_delta_pack(spf_route_table* t, spf_route_delta_sizes* sizes)
     t->pk.link_words = tot[2];
     t->pk.link_metrics = t->lfa ? tot[3] : 0;
     if (t->pk.cells || t->pk.gone) {
-      int st = SPF_OK;
-      if ((st = grow_dev(&t->d_pk_cell, &t->pk_cell_cap, (size_t)t->pk.cells * 3)) ||
-          (st = grow_dev(&t->d_pk_links, &t->pk_links_cap, (size_t)t->pk.link_words)) ||
-          (st = grow_dev(&t->d_pk_lmet, &t->pk_lmet_cap, (size_t)t->pk.link_metrics)) ||
-          (st = grow_dev(&t->d_pk_gone, &t->pk_gone_cap, (size_t)t->pk.gone))) {
-        return st;
+      if (t->d_pk_cell.reserve((size_t)t->pk.cells * 3) != hipSuccess ||
+          t->d_pk_links.reserve((size_t)t->pk.link_words) != hipSuccess ||
+          t->d_pk_lmet.reserve((size_t)t->pk.link_metrics) != hipSuccess ||
+          t->d_pk_gone.reserve((size_t)t->pk.gone) != hipSuccess) {
+        return fail(SPF_E_NOMEM, "route delta buffer");
       }
       RouteDeltaFillArgs a{};
       a.bits = t->d_diff;
@@ -15383,7 +15381,7 @@ int spf_route_table_delta_pack(spf_route_table* t, spf_route_delta_sizes* sizes)
       a.best = t->d_best;
       a.links = t->d_links;
       a.lk_off = t->d_lk_off;
-      a.lmet = t->lfa ? t->d_lmet : nullptr;
+      a.lmet = t->lfa ? t->d_lmet.p : nullptr;
       a.lm_off = t->d_lm_off;
       a.P = P;
       a.nq = nq;
@@ -15483,13 +15481,12 @@ int spf_route_table_fetch_cells(
   }
   spf_graph* g = t->q->g;
   HIP_TRY(hipSetDevice(g->device));
-  int st = SPF_OK;
-  if ((st = grow_dev(&t->d_gc_idx, &t->gc_idx_cap, (size_t)n * 2)) ||
-      (st = grow_dev(&t->d_gc_pos, &t->gc_pos_cap, pos.size())) ||
-      (st = grow_dev(&t->d_gc_out, &t->gc_out_cap, (size_t)n * 2)) ||
-      (st = grow_dev(&t->d_gc_links, &t->gc_links_cap, (size_t)nl)) ||
-      (st = grow_dev(&t->d_gc_lmet, &t->gc_lmet_cap, (size_t)nm))) {
-    return st;
+  if (t->d_gc_idx.reserve((size_t)n * 2) != hipSuccess ||
+      t->d_gc_pos.reserve(pos.size()) != hipSuccess ||
+      t->d_gc_out.reserve((size_t)n * 2) != hipSuccess ||
+      t->d_gc_links.reserve((size_t)nl) != hipSuccess ||
+      t->d_gc_lmet.reserve((size_t)nm) != hipSuccess) {
+    return fail(SPF_E_NOMEM, "route delta buffer");
   }
   // the staging buffers are reused by the next call: every copy below has
   // landed (stream order, then the final synchronise) before this one returns

@@ -300,6 +300,71 @@ def test_second_diff_then_pack_returns_the_second_result(gpu_ready):
         B.close()
 
 
+def _check_cells(N, rows, cols):
+    """fetch_cells(rows, cols) of N against indexing fetch(i) / fetch_link_metrics(i)."""
+    degs = [len(r) for r in N.rows]
+    metric, best, links, lmet = N.t.fetch_cells(rows, cols, degs)
+    row = {i: N.t.fetch(i) for i in set(rows)}
+    xs = {i: N.t.fetch_link_metrics(i, degs[i]) for i in set(rows)} if N.lfa else {}
+    lo = mo = 0
+    for k, (i, p) in enumerate(zip(rows, cols)):
+        m, b, words = row[i]
+        assert (metric[k], best[k]) == (m[p], b[p]), k
+        W = N.t.link_words(i)
+        assert links[lo:lo + W].tolist() == words[p].tolist(), k
+        lo += W
+        if N.lfa:
+            assert lmet[mo:mo + degs[i]].tolist() == xs[i][p].tolist(), k
+            mo += degs[i]
+    assert lo == len(links) and mo == len(lmet)
+
+
+@pytest.mark.parametrize("lfa", [False, True])
+def test_staging_grows_and_is_reused_at_a_smaller_size(gpu_ready, lfa):
+    """One newer table B (the 8x8 grid, node 20 drained so that cells change
+    too) diffed against an older table with 1 extra column, then one with 130
+    (130 gone columns: three gone-bitmap words per row instead of one, a longer
+    map stage, a longer packed list), then the first again: the grow-only
+    staging of B is grown and then reused at the smaller size, and the third
+    pack equals the first.  The same for the gather staging of fetch_cells:
+    1 cell, 300 cells, 1 cell.  Every extra column is announced by one node,
+    so it has a route in the 63 other rows."""
+    links = grid_links(8)
+    ov = np.zeros(64, dtype=np.uint8)
+    ov[20] = 1
+    extra = [[(7 * k + 3) % 64] for k in range(130)]
+    B = Net(64, links, GRID_ANN, lfa, overloaded=ov)
+    A1 = Net(64, links, GRID_ANN + extra[:1], lfa)
+    A2 = Net(64, links, GRID_ANN + extra, lfa)
+    try:
+        ident = np.arange(64, dtype=np.uint32)
+        cols = np.arange(B.P, dtype=np.uint32)
+        packs = []
+        for A in (A1, A2, A1):
+            gone = list(range(B.P, A.P))
+            counts, _, gn = run_mapped(A, B, ident, cols, gone, ident, link_maps(A, B, ident), {})
+            got = check_pack(B, mapped=True)
+            assert got["cells"] > 0 and got["num_gone"] == gn.sum() == 63 * len(gone)
+            assert got["cell_off"][-1] + got["gone_off"][-1] == counts.sum()
+            packs.append(got)
+        for k, first in packs[0].items():
+            assert np.array_equal(packs[2][k], first), k
+        assert packs[1]["num_gone"] == 130 * packs[0]["num_gone"]
+        # the gather staging: small, large (cells repeated across rows and columns), small
+        rng = np.random.RandomState(7)
+        rows = rng.randint(0, 64, size=300).tolist()
+        pcols = rng.randint(0, B.P, size=300).tolist()
+        rows[100:110] = [rows[0]] * 10
+        pcols[100:110] = [pcols[0]] * 10
+        _check_cells(B, [9], [65])
+        _check_cells(B, rows, pcols)
+        _check_cells(B, [9], [65])
+    finally:
+        A1.close()
+        A2.close()
+        B.close()
+
+
 def _fetch_status(t, z):
     """spf_route_table_delta_fetch into buffers sized by z: the status."""
     u64 = lambda n: np.zeros(max(int(n), 1), dtype=np.uint64)  # noqa: E731
