@@ -490,8 +490,9 @@ int spf_route_table_select_elapsed_ms(spf_route_table* t, float* ms);
  * is a next-hop destination).  Unselected columns and cells without a route
  * read igp UINT32_MAX, winners 0; in a selected column `best` is the fold's
  * best candidate.  spf_route_table_diff and _diff_mapped compare metric,
- * best and links as for any column and ignore the igp word (the host layer's
- * AllNodesRouteTable::diff refuses tables with BGP columns altogether). */
+ * best and links as for any column and, in a column selected in both tables,
+ * the igp word too (a cell with a route on both sides whose igp differs is
+ * changed: bestNexthop.metric is part of RibUnicastEntry equality). */
 int spf_route_table_fetch_sel(
     spf_route_table* t, uint32_t i, uint32_t* metric, uint32_t* best, uint64_t* links,
     uint32_t* igp, uint32_t* winners);
@@ -502,8 +503,17 @@ int spf_route_table_fetch_sel(
  * best announcer or link mask differs — getRouteDelta's (Decision.cpp:47-85)
  * unicast updates and deletes for every node at once.  changed[i] = changed
  * prefixes of row i (host [num rows]); the per-row bitmap is kept in `newer`
- * (spf_route_table_changed).  SPF_E_UNSUPPORTED if the layouts differ. */
+ * (spf_route_table_changed).  SPF_E_UNSUPPORTED if the layouts differ, or if
+ * the two tables do not select the same columns (spf_route_table_create_sel). */
 int spf_route_table_diff(spf_route_table* older, spf_route_table* newer, uint32_t* changed);
+/* SPF_RT_LFA tables: with `on` non-zero, later diffs whose `newer` is `t`
+ * (spf_route_table_diff and _diff_mapped) use the metric word to tell route
+ * from no route only.  Every next hop of an LFA cell has its own metric
+ * (spf_route_table_fetch_link_metrics), which the diff compares link by link;
+ * the cell's metric, the shortest distance, is in no next hop's place, and a
+ * drained neighbour can raise it while the route stays the same.  Off by
+ * default.  SPF_E_INVALID on a table without SPF_RT_LFA. */
+int spf_route_table_diff_routes(spf_route_table* t, int on);
 /* Changed-prefix bitmap of row i from the last diff: bits[ceil(P/64)]. */
 int spf_route_table_changed(spf_route_table* t, uint32_t i, uint64_t* bits);
 
@@ -522,7 +532,10 @@ typedef struct spf_route_diff_map {
                                 its link count long, or empty: identity for that row */
   const uint32_t* dirty_off; /* [newer P + 1]: offsets into dirty_ann */
   const uint32_t* dirty_ann; /* newer node ids: announcers of the column whose prefix entry
-                                changed (a route whose best is one of them is an update) */
+                                changed (a route whose best is one of them is an update).
+                                An entry SPF_MAP_NONE marks a column whose best announcer is
+                                no part of the route (a BGP column selected once for all
+                                nodes): best is not compared in that column */
   uint32_t num_gone;
 } spf_route_diff_map;
 /* The route delta of every node (getRouteDelta, Decision.cpp:47-85) between
@@ -538,9 +551,10 @@ typedef struct spf_route_diff_map {
  * newer columns + deleted gone columns of row i; the bitmaps are kept in
  * `newer`.  Rows whose links keep their positions compare mask words like
  * spf_route_table_diff; a remapped row may have at most 1024 links.
- * SPF_E_INVALID for an out-of-range entry or a col_of / link_of that is not
- * injective, SPF_E_UNSUPPORTED when the tables differ in SPF_RT_LFA or in
- * device.  A null `map` is all identity. */
+ * SPF_E_INVALID for an out-of-range entry, a col_of / link_of that is not
+ * injective or a col_of that pairs a selected column with an unselected one,
+ * SPF_E_UNSUPPORTED when the tables differ in SPF_RT_LFA or in device.  A
+ * null `map` is all identity. */
 int spf_route_table_diff_mapped(
     spf_route_table* older, spf_route_table* newer, const spf_route_diff_map* map,
     uint32_t* changed);
@@ -582,6 +596,12 @@ int spf_route_table_delta_fetch(
     uint64_t* cell_off /*[rows+1]*/, uint32_t* col, uint32_t* metric, uint32_t* best /*[cells]*/,
     uint64_t* links /*[link_words]*/, uint32_t* link_metrics /*[link_metrics], NULL unless LFA*/,
     uint64_t* gone_off /*[rows+1]*/, uint32_t* gone /*[gone]: index g into gone_cols*/);
+/* Tables with selected columns: the pack also copies every changed cell's igp
+ * word (UINT32_MAX in an unselected column, as spf_route_table_fetch_sel
+ * reads), in the packed list's order.  Same staleness rules as
+ * spf_route_table_delta_fetch; SPF_E_UNSUPPORTED on a table without selected
+ * columns. */
+int spf_route_table_delta_fetch_igp(spf_route_table* newer, uint32_t* igp /*[cells]*/);
 /* Sparse read of any run table: cell k = (rows[k], cols[k]) (repeats allowed).
  * Links and link metrics are packed in list order, link_words(rows[k]) /
  * deg(rows[k]) each (link_metrics: SPF_RT_LFA tables only, else NULL).  What
@@ -591,6 +611,11 @@ int spf_route_table_delta_fetch(
 int spf_route_table_fetch_cells(
     spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols,
     uint32_t* metric, uint32_t* best, uint64_t* links, uint32_t* link_metrics);
+/* The igp word of the same kind of list (UINT32_MAX in an unselected column).
+ * Same checks as spf_route_table_fetch_cells; SPF_E_UNSUPPORTED on a table
+ * without selected columns. */
+int spf_route_table_fetch_cells_igp(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* igp);
 
 /* ---- multi-GPU all-sources tables ----
  * The reference computes every SpfResult on the one Decision thread

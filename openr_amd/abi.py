@@ -99,6 +99,9 @@ EXPORTED_SYMBOLS = (
     "spf_route_table_delta_pack",
     "spf_route_table_delta_fetch",
     "spf_route_table_fetch_cells",
+    "spf_route_table_delta_fetch_igp",
+    "spf_route_table_fetch_cells_igp",
+    "spf_route_table_diff_routes",
     "spf_cluster_unique_id",
     "spf_cluster_create_local",
     "spf_cluster_create_rank",
@@ -421,6 +424,9 @@ def load():
                                                   pu32]),
         "spf_route_table_fetch_cells": (C.c_int, [vp, C.c_uint64, pu32, pu32, pu32, pu32, pu64,
                                                   pu32]),
+        "spf_route_table_delta_fetch_igp": (C.c_int, [vp, pu32]),
+        "spf_route_table_diff_routes": (C.c_int, [vp, C.c_int]),
+        "spf_route_table_fetch_cells_igp": (C.c_int, [vp, C.c_uint64, pu32, pu32, pu32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
@@ -1123,6 +1129,35 @@ class RouteTable:
             _p(metric, C.c_uint32), _p(best, C.c_uint32), _p(links, C.c_uint64),
             _p(lmet, C.c_uint32) if self.lfa else None), "spf_route_table_fetch_cells")
         return metric[:n], best[:n], links[:nl], lmet[:nm]
+
+    def diff_routes(self, on: bool = True):
+        """spf_route_table_diff_routes (SPF_RT_LFA tables): later diffs into
+        this table use the metric word for route / no route only."""
+        _check(load().spf_route_table_diff_routes(self.h, 1 if on else 0),
+               "spf_route_table_diff_routes")
+        return self
+
+    def delta_fetch_igp(self, cells: int) -> np.ndarray:
+        """spf_route_table_delta_fetch_igp: the igp word of every cell of the
+        packed list (`cells` of them, as the pack returned; UINT32_MAX in an
+        unselected column).  Tables with selected columns only."""
+        igp = np.zeros(max(cells, 1), dtype=np.uint32)
+        _check(load().spf_route_table_delta_fetch_igp(self.h, _p(igp, C.c_uint32)),
+               "spf_route_table_delta_fetch_igp")
+        return igp[:cells]
+
+    def fetch_cells_igp(self, rows, cols) -> np.ndarray:
+        """spf_route_table_fetch_cells_igp: the igp word of the cells
+        (rows[k], cols[k]).  Tables with selected columns only."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        n = len(rows)
+        assert len(cols) == n
+        igp = np.zeros(max(n, 1), dtype=np.uint32)
+        _check(load().spf_route_table_fetch_cells_igp(
+            self.h, n, _p(rows, C.c_uint32) if n else None, _p(cols, C.c_uint32) if n else None,
+            _p(igp, C.c_uint32)), "spf_route_table_fetch_cells_igp")
+        return igp[:n]
 
 
 # ------------------------------------------------- multi-GPU tables (RCCL)

@@ -363,6 +363,14 @@ void AllNodesRouteTable::createAndRunTable(
     tableFailure("spf_route_table_create", s);
   }
   table_.reset(table);
+  if (lfa_) {
+    // every LFA next hop carries its own metric (compared link by link): the
+    // cell's metric word, the shortest distance, is no part of a route, and a
+    // drained neighbour can raise it while the route stays the same
+    if ((s = spf_route_table_diff_routes(table_.get(), 1)) != SPF_OK) {
+      tableFailure("spf_route_table_diff_routes", s);
+    }
+  }
   Counters::add("decision.route_table_create_us", usSince(tp));
   tp = std::chrono::steady_clock::now();
   if ((s = spf_route_table_run(table_.get())) != SPF_OK) {
@@ -380,7 +388,12 @@ AllNodesRouteTable::AllNodesRouteTable(
     const LinkState& ls, const PrefixState& ps, bool enableV4, bool computeLfa,
     const std::unordered_set<std::string>* borderNodes, bool bgpColumns, bool bgpDryRun,
     bool bgpUseIgpMetric)
-    : area_(ls.getArea()), enableV4_(enableV4), lfa_(computeLfa), bgpDryRun_(bgpDryRun) {
+    : area_(ls.getArea()),
+      enableV4_(enableV4),
+      lfa_(computeLfa),
+      bgpColumns_(bgpColumns),
+      bgpDryRun_(bgpDryRun),
+      bgpIgp_(bgpUseIgpMetric) {
   auto tp = std::chrono::steady_clock::now();
   LinkState::Engine& eng = ls.engine();
   Counters::add("decision.route_table_engine_us", usSince(tp));
@@ -674,17 +687,26 @@ std::unordered_map<int32_t, RibMplsEntry> AllNodesRouteTable::mplsRoutes(
   return out;
 }
 
+// what a host-selected BGP column puts into every route of the column
+// (bestArea is not part of RibUnicastEntry equality)
+bool AllNodesRouteTable::sameSelection(const BgpSel& a, const BgpSel& b) {
+  return a.bestEntry == b.bestEntry && a.bestNexthop == b.bestNexthop;
+}
+
 std::vector<uint32_t> AllNodesRouteTable::diff(const AllNodesRouteTable& older) {
   bool sameOwners = older.owners_.size() == owners_.size();
   for (size_t k = 0; sameOwners && k < owners_.size(); ++k) {
     sameOwners = older.owners_[k].label == owners_[k].label && older.owners_[k].id == owners_[k].id;
   }
-  if (nbgp_ || older.nbgp_) {
-    throw std::invalid_argument(
-        "AllNodesRouteTable::diff: tables with BGP columns (AllAreasRouteTable) are not diffed");
-  }
   if (older.lfa_ != lfa_ || older.area_ != area_) {
     throw std::invalid_argument("AllNodesRouteTable::diff: different areas or LFA modes");
+  }
+  if (older.bgpColumns_ != bgpColumns_ || older.bgpDryRun_ != bgpDryRun_ ||
+      older.bgpIgp_ != bgpIgp_) {
+    // doNotInstall would flip every BGP route; a selected and a host-selected
+    // column are not comparable cell by cell
+    throw std::invalid_argument(
+        "AllNodesRouteTable::diff: different bgpColumns, bgpDryRun or bgpUseIgpMetric");
   }
   if (older.names_ != names_ || older.prefixes_ != prefixes_ || older.row_ != row_ ||
       !sameOwners) {
@@ -698,6 +720,26 @@ std::vector<uint32_t> AllNodesRouteTable::diff(const AllNodesRouteTable& older) 
         if (o.id == a.id && !(o.entry == a.entry)) {
           return diffMapped(older);
         }
+      }
+    }
+    // BGP columns: another kind of column, another host-side selection or
+    // other candidates (their order, pair codes or loopbacks) likewise
+    if (columnKind(p) != older.columnKind(p)) {
+      return diffMapped(older);
+    }
+    if (bgp_[p] || sel_[p]) {
+      bool same = announcers_[p].size() == older.announcers_[p].size();
+      for (size_t c = 0; same && c < announcers_[p].size(); ++c) {
+        same = announcers_[p][c].id == older.announcers_[p][c].id;
+      }
+      if (same && bgp_[p]) {
+        same = sameSelection(*bgp_[p], *older.bgp_[p]);
+      }
+      if (same && sel_[p]) {
+        same = sel_[p]->pair == older.sel_[p]->pair && sel_[p]->via == older.sel_[p]->via;
+      }
+      if (!same) {
+        return diffMapped(older);
       }
     }
   }
@@ -714,6 +756,7 @@ std::vector<uint32_t> AllNodesRouteTable::diff(const AllNodesRouteTable& older) 
   diffed_ = true;
   mapped_ = false;
   goneCols_.clear();
+  goneNew_.clear();
   rowOf_.resize(names_.size());
   for (uint32_t i = 0; i < rowOf_.size(); ++i) {
     rowOf_[i] = i;
@@ -736,7 +779,8 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
     }
   }
   // columns: unicast by prefix, node labels by (label, owner name)
-  std::vector<uint32_t> colOf(C, SPF_MAP_NONE), gone;
+  std::vector<uint32_t> colOf(C, SPF_MAP_NONE), gone, goneNew;
+  std::unordered_map<uint32_t, uint32_t> newOfOld; // older column -> newer one of another kind
   std::vector<uint8_t> kept(Ca, 0);
   {
     std::unordered_map<thrift::IpPrefix, uint32_t> colA;
@@ -746,10 +790,18 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
     }
     for (size_t p = 0; p < P; ++p) {
       auto it = colA.find(prefixes_[p]);
-      if (it != colA.end()) {
-        colOf[p] = it->second;
-        kept[it->second] = 1;
+      if (it == colA.end()) {
+        continue;
       }
+      if (columnKind(p) != older.columnKind(it->second)) {
+        // Open/R, host-selected BGP, selected: another kind of column has no
+        // counterpart -- the older one is gone, and a node with a route on
+        // both sides gets one update (unicastDelta drops the delete)
+        newOfOld.emplace(it->second, (uint32_t)p);
+        continue;
+      }
+      colOf[p] = it->second;
+      kept[it->second] = 1;
     }
     std::map<std::pair<int32_t, uint32_t>, uint32_t> labA; // (label, newer owner id) -> column
     for (size_t k = 0; k < older.owners_.size(); ++k) {
@@ -768,6 +820,8 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
     for (uint32_t c = 0; c < Ca; ++c) {
       if (!kept[c]) {
         gone.push_back(c);
+        auto it = newOfOld.find(c);
+        goneNew.push_back(it == newOfOld.end() ? SPF_MAP_NONE : it->second);
       }
     }
   }
@@ -819,15 +873,34 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
       linkOff[i + 1] = (uint32_t)linkOf.size();
     }
   }
-  // dirty announcers: same node, PrefixEntry unequal
+  // dirty announcers: same node, PrefixEntry unequal.  A BGP column selected
+  // on the host has the selection's best entry and loopback at every node:
+  // if either differs every announcer is dirty (the cell's best is one of
+  // them, so every routed cell is an update); the cell's own best is no part
+  // of its routes (the SPF_MAP_NONE entry).  A candidate of a selected column
+  // is dirty when its entry or its loopback differs.
   std::vector<uint32_t> dirtyOff(C + 1, 0), dirtyAnn;
   for (size_t p = 0; p < C; ++p) {
     if (p < P && colOf[p] != SPF_MAP_NONE) {
-      const auto& olds = older.announcers_[colOf[p]];
-      for (const auto& a : announcers_[p]) {
-        for (const auto& o : olds) {
-          if (nodeOf[o.id] == a.id && !(o.entry == a.entry)) {
+      const uint32_t pa = colOf[p];
+      const auto& olds = older.announcers_[pa];
+      if (bgp_[p]) {
+        dirtyAnn.push_back(SPF_MAP_NONE);
+        if (!sameSelection(*bgp_[p], *older.bgp_[pa])) {
+          for (const auto& a : announcers_[p]) {
             dirtyAnn.push_back(a.id);
+          }
+        }
+      } else {
+        for (size_t c = 0; c < announcers_[p].size(); ++c) {
+          const auto& a = announcers_[p][c];
+          for (size_t b = 0; b < olds.size(); ++b) {
+            const auto& o = olds[b];
+            if (nodeOf[o.id] == a.id &&
+                (!(o.entry == a.entry) ||
+                 (sel_[p] && !(sel_[p]->via[c] == older.sel_[pa]->via[b])))) {
+              dirtyAnn.push_back(a.id);
+            }
           }
         }
       }
@@ -864,10 +937,54 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
     tableFailure("spf_route_table_diff_mapped", s);
   }
   diffCallMs_ = (float)usSince(tp) / 1000.f;
+  // a column that changed its kind: a node with a route on both sides was
+  // counted twice (gone + new) and gets one update
+  std::vector<uint32_t> rows, colsNew, colsOld;
+  for (size_t g = 0; g < gone.size(); ++g) {
+    for (uint32_t i = 0; goneNew[g] != SPF_MAP_NONE && i < V; ++i) {
+      if (rowOf[i] != SPF_MAP_NONE) {
+        rows.push_back(i);
+        colsNew.push_back(goneNew[g]);
+        colsOld.push_back(gone[g]);
+      }
+    }
+  }
+  if (!rows.empty()) {
+    auto routed = [](const AllNodesRouteTable& t, const std::vector<uint32_t>& rs,
+                         const std::vector<uint32_t>& cs) {
+      uint64_t nl = 0, nm = 0;
+      for (const uint32_t r : rs) {
+        const uint64_t deg = t.row_[r + 1] - t.row_[r];
+        nl += (deg + 63) / 64;
+        nm += t.lfa_ ? deg : 0;
+      }
+      std::vector<uint32_t> metric(rs.size()), best(rs.size()), lmet(std::max<uint64_t>(nm, 1));
+      std::vector<uint64_t> links(std::max<uint64_t>(nl, 1));
+      if (int s = spf_route_table_fetch_cells(
+              t.table_.get(), rs.size(), rs.data(), cs.data(), metric.data(), best.data(),
+              links.data(), t.lfa_ ? lmet.data() : nullptr);
+          s != SPF_OK) {
+        tableFailure("spf_route_table_fetch_cells", s);
+      }
+      return metric;
+    };
+    std::vector<uint32_t> oldRows(rows.size());
+    for (size_t k = 0; k < rows.size(); ++k) {
+      oldRows[k] = rowOf[rows[k]];
+    }
+    const auto mn = routed(*this, rows, colsNew);
+    const auto mo = routed(older, oldRows, colsOld);
+    for (size_t k = 0; k < rows.size(); ++k) {
+      if (mn[k] != 0xFFFFFFFFu && mo[k] != 0xFFFFFFFFu) {
+        changed[rows[k]] -= 1;
+      }
+    }
+  }
   diffed_ = true;
   mapped_ = true;
   rowOf_ = std::move(rowOf);
   goneCols_ = std::move(gone);
+  goneNew_ = std::move(goneNew);
   older_ = &older;
   return changed;
 }
@@ -897,6 +1014,10 @@ std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string
       tableFailure("spf_route_table_changed_gone", s);
     }
     forEachSetBit(gbits.data(), gbits.size(), [&](size_t g) {
+      const uint32_t p = goneNew_[g];
+      if (p != SPF_MAP_NONE && ((bits[p / 64] >> (p % 64)) & 1)) {
+        return; // the column changed its kind: counted as the update already
+      }
       (goneCols_[g] < older_->prefixes_.size() ? uni : lab) += 1;
     });
   }
@@ -946,7 +1067,9 @@ void AllNodesRouteTable::unicastDelta(
   const size_t P = prefixes_.size(), Pa = older_->prefixes_.size();
   for (size_t k = 0; k < ng; ++k) {
     const uint32_t c = goneCols_[gone[k]];
-    if (c < Pa) {
+    // (a column that changed its kind and still has a route here: the update
+    // below replaces the older route)
+    if (c < Pa && !std::binary_search(cols, cols + n, goneNew_[gone[k]])) {
       u.unicastRoutesToDelete.push_back(older_->prefixes_[c]);
     }
   }
@@ -1029,7 +1152,8 @@ uint64_t AllNodesRouteTable::deltaFetchBytes(const std::string& node) const {
   auto rowBytes = [](const AllNodesRouteTable& t, uint32_t r) {
     const uint64_t C = t.prefixes_.size() + t.owners_.size();
     const uint64_t deg = t.row_[r + 1] - t.row_[r];
-    return C * (8 + ((deg + 63) / 64) * 8 + (t.lfa_ ? deg * 4 : 0));
+    // (tables with selected columns: the row's igp and winners words too)
+    return C * (8 + ((deg + 63) / 64) * 8 + (t.lfa_ ? deg * 4 : 0)) + (uint64_t)t.nsel_ * 8;
   };
   const uint64_t C = prefixes_.size() + owners_.size();
   uint64_t b = ((C + 63) / 64) * 8 + rowBytes(*this, i);
@@ -1070,6 +1194,13 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
           lfa_ ? lmet.data() : nullptr, goneOff.data(), gone.data());
       s != SPF_OK) {
     tableFailure("spf_route_table_delta_fetch", s);
+  }
+  // selected columns: the igp lane of the packed list (bestNexthop.metric)
+  std::vector<uint32_t> igp(nsel_ ? z.cells : 0);
+  if (nsel_) {
+    if (int s = spf_route_table_delta_fetch_igp(table_.get(), igp.data()); s != SPF_OK) {
+      tableFailure("spf_route_table_delta_fetch_igp", s);
+    }
   }
   const auto t2 = Clock::now();
   auto degOf = [](const AllNodesRouteTable& t, uint32_t r) {
@@ -1150,7 +1281,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
   // a sparse Row over cells [k0, k1) of one node in a cell list
   auto view = [&](const AllNodesRouteTable& t, uint32_t r, const uint32_t* cols,
                   const uint32_t* metric, const uint32_t* best, size_t n, const uint64_t* links,
-                  const uint32_t* lmet) {
+                  const uint32_t* lmet, const uint32_t* igp = nullptr) {
     Row v;
     v.sparse = true;
     v.deg = degOf(t, r);
@@ -1161,6 +1292,9 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
     v.links.assign(links, links + n * v.W);
     if (lfa_) {
       v.lmet.assign(lmet, lmet + n * v.deg);
+    }
+    if (igp) {
+      v.igp.assign(igp, igp + n);
     }
     return v;
   };
@@ -1174,7 +1308,8 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
     const uint64_t k0 = cellOff[i], k1 = cellOff[i + 1];
     const Row r = k1 > k0
         ? view(*this, i, col.data() + k0, metric.data() + k0, best.data() + k0, (size_t)(k1 - k0),
-               links.data() + lwBase[i], lmet.data() + lmBase[i])
+               links.data() + lwBase[i], lmet.data() + lmBase[i],
+               nsel_ ? igp.data() + k0 : nullptr)
         : Row{};
     unicastDelta(i, r, col.data() + k0, (size_t)(k1 - k0), gone.data() + goneOff[i],
                  (size_t)(goneOff[i + 1] - goneOff[i]), u);
@@ -1208,7 +1343,8 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
   st.olderCells = co.rows.size();
   // what crossed from the device: the pack's totals, the packed list, and per
   // gathered cell its metric and best, plus the link words and link metrics
-  st.bytes = 32 + 2 * ((uint64_t)V + 1) * 8 + z.cells * 12 + z.link_words * 8 +
+  // (tables with selected columns: the igp lane, one more word per cell)
+  st.bytes = 32 + 2 * ((uint64_t)V + 1) * 8 + z.cells * (nsel_ ? 16 : 12) + z.link_words * 8 +
       z.link_metrics * 4 + z.gone * 4 + (st.newerCells + st.olderCells) * 8 +
       (cn.links.size() + co.links.size()) * 8 + (cn.lmet.size() + co.lmet.size()) * 4;
   lastDeltas_ = st;
@@ -1275,6 +1411,11 @@ AllAreasRouteTable::AllAreasRouteTable(
 }
 
 AllAreasRouteTable::~AllAreasRouteTable() = default;
+
+const AllNodesRouteTable* AllAreasRouteTable::areaTable(const std::string& area) const {
+  auto it = tables_.find(area);
+  return it == tables_.end() ? nullptr : it->second.get();
+}
 
 std::optional<DecisionRouteDb> AllAreasRouteTable::routeDb(const std::string& node) const {
   lastTable_ = lastHost_ = 0;

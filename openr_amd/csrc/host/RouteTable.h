@@ -41,6 +41,7 @@
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "LinkState.h"
@@ -68,7 +69,7 @@ class AllNodesRouteTable {
   // among them gets no route (selectEcmpBgp :805-866).  bestPrefixEntry,
   // bestArea and the loopback next hop are the selection's; doNotInstall =
   // bgpDryRun.  A prefix with an announcer some node cannot reach stays on
-  // the host.  diff() refuses tables with BGP columns.
+  // the host.
   // bgpUseIgpMetric (with bgpColumns): the selection differs per node --
   // every candidate's vector gets an OPENR_IGP_COST entity holding -d(node,
   // announcer) before the fold (Decision.cpp:746-766) -- so a BGP prefix
@@ -120,8 +121,23 @@ class AllNodesRouteTable {
   // addresses, interface or area (what materialise reads) differ has no
   // counterpart, so every route over it is changed -- and announcers whose
   // PrefixEntry differs are the column's dirty list.  A node the older table
-  // lacks has every route changed.  Throws std::invalid_argument for BGP
-  // columns, different areas or different LFA modes.
+  // lacks has every route changed.
+  // BGP columns are compared like any other, plus what their routes hold
+  // beyond the cell: in a selected column the cell's igp word
+  // (bestNexthop.metric: the device diff compares it) and each candidate's
+  // entry and loopback (dirty when they differ); in a host-selected column
+  // the selection's best entry and loopback (every announcer dirty when they
+  // differ; the cell's own best is not compared).  Any such difference, other
+  // candidates or pair codes go through the maps.  A prefix whose column
+  // kind differs between the tables (Open/R, host-selected, selected) has no
+  // counterpart: the older column is gone and a node with a route on both
+  // sides gets one update.
+  // LFA tables: the cell's metric word (the shortest distance) is no part of
+  // a route whose next hops carry their own metrics, so the table asks the
+  // device diff to leave it out (spf_route_table_diff_routes): a drained
+  // neighbour can raise it while every link keeps its bit and its metric.
+  // Throws std::invalid_argument for different areas, LFA modes, bgpColumns,
+  // bgpDryRun or bgpUseIgpMetric.
   std::vector<uint32_t> diff(const AllNodesRouteTable& older);
   // (changed unicast prefixes, changed node-label columns) of `node` from
   // the last diff; .first == unicast updates + deletes of delta(node)
@@ -144,7 +160,8 @@ class AllNodesRouteTable {
   // `older` must outlive this call.
   std::vector<DecisionRouteUpdate> deltas() const;
   // the last deltas(): wall time of its steps, the packed sizes, the cells
-  // gathered from either table and the bytes copied from the device
+  // gathered from either table and the bytes copied from the device (with
+  // selected columns the packed list has a fourth lane, the cells' igp)
   struct DeltasStats {
     double packUs = 0, fetchUs = 0, gatherUs = 0, assembleUs = 0, totalUs = 0;
     uint64_t cells = 0, gone = 0, linkWords = 0, linkMetrics = 0;
@@ -280,7 +297,10 @@ class AllNodesRouteTable {
   void collectAdjLabels(const LinkState& ls);
   void createAndRunTable(const std::vector<uint32_t>& annOff, const std::vector<uint32_t>& ann);
   size_t nbgp_{0}, nsel_{0};
-  bool bgpDryRun_{false};
+  bool bgpColumns_{false}, bgpDryRun_{false}, bgpIgp_{false};
+  // 0 Open/R, 1 BGP selected on the host, 2 a selected column
+  int columnKind(size_t p) const { return sel_[p] ? 2 : bgp_[p] ? 1 : 0; }
+  static bool sameSelection(const BgpSel& a, const BgpSel& b);
   // node-label columns: column prefixes_.size() + k is owners_[k]
   struct LabelOwner {
     int32_t label;
@@ -304,6 +324,9 @@ class AllNodesRouteTable {
   bool mapped_{false};
   std::vector<uint32_t> rowOf_;
   std::vector<uint32_t> goneCols_;
+  // parallel to goneCols_: the newer column of the same prefix when the
+  // column changed its kind, else SPF_MAP_NONE
+  std::vector<uint32_t> goneNew_;
   float diffCallMs_{0};
   mutable DeltasStats lastDeltas_;
   std::vector<uint32_t> diffMapped(const AllNodesRouteTable& older);
@@ -352,6 +375,16 @@ class AllAreasRouteTable {
   size_t lastTableRoutes() const { return lastTable_; }
   size_t lastHostRoutes() const { return lastHost_; }
   bool isBorder(const std::string& node) const { return border_.count(node) > 0; }
+  // the device table of `area` (null: unknown area, or one left to the host),
+  // so that a holder of two all-areas tables can diff the device share per
+  // area; a whole all-areas delta with border nodes and the host share is
+  // not built here
+  const AllNodesRouteTable* areaTable(const std::string& area) const;
+  // (diff() keeps its bitmaps in the newer table: the holder of a non-const
+  // all-areas table diffs through this one)
+  AllNodesRouteTable* areaTable(const std::string& area) {
+    return const_cast<AllNodesRouteTable*>(std::as_const(*this).areaTable(area));
+  }
   size_t numTables() const { return tables_.size(); }
   // BGP prefixes the device tables serve (round 6; AllNodesRouteTable
   // bgpColumns)

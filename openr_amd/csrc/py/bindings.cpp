@@ -438,7 +438,10 @@ PYBIND11_MODULE(_openr_spf, m) {
       })
       .def_property_readonly("route_ms", &AllAreasRouteTable::routeMs)
       .def_property_readonly("select_ms", &AllAreasRouteTable::selectMs)
-      .def("is_border", &AllAreasRouteTable::isBorder);
+      .def("is_border", &AllAreasRouteTable::isBorder)
+      .def("area_table",
+           [](AllAreasRouteTable& t, const std::string& area) { return t.areaTable(area); },
+           py::arg("area"), py::return_value_policy::reference_internal);
 
   py::class_<AllSourcesTable>(m, "AllSourcesTable")
       .def(py::init([](const AreaMapHolder& areas, const std::string& area, std::vector<int> devices,
@@ -474,13 +477,27 @@ PYBIND11_MODULE(_openr_spf, m) {
 
   py::class_<AllNodesRouteTable>(m, "AllNodesRouteTable")
       .def(py::init([](const AreaMapHolder& areas, const std::string& area, const PrefixState& ps,
-                       bool enableV4, bool lfa) {
-             return std::make_unique<AllNodesRouteTable>(areas.map.at(area), ps, enableV4, lfa);
+                       bool enableV4, bool lfa, bool bgpColumns, bool bgpDryRun,
+                       bool bgpUseIgpMetric) {
+             return std::make_unique<AllNodesRouteTable>(areas.map.at(area), ps, enableV4, lfa,
+                                                         nullptr, bgpColumns, bgpDryRun,
+                                                         bgpUseIgpMetric);
            }),
            py::arg("areas"), py::arg("area"), py::arg("prefix_state"), py::arg("enable_v4") = true,
-           py::arg("lfa") = false, py::keep_alive<1, 2>())
+           py::arg("lfa") = false, py::arg("bgp_columns") = false, py::arg("bgp_dry_run") = false,
+           py::arg("bgp_use_igp_metric") = false, py::keep_alive<1, 2>())
       .def_property_readonly("num_nodes", &AllNodesRouteTable::numNodes)
       .def_property_readonly("num_prefixes", &AllNodesRouteTable::numPrefixes)
+      .def_property_readonly("num_bgp_prefixes", &AllNodesRouteTable::numBgpPrefixes)
+      .def_property_readonly("num_selected_columns", &AllNodesRouteTable::numSelectedColumns)
+      .def_property_readonly("prefixes", [](const AllNodesRouteTable& t) {
+        // the served unicast prefixes, as the keys routes() uses
+        py::list out;
+        for (const auto& p : t.prefixes()) {
+          out.append(prefixKey(p));
+        }
+        return out;
+      })
       .def_property_readonly("spf_ms", &AllNodesRouteTable::spfMs)
       .def_property_readonly("route_ms", &AllNodesRouteTable::routeMs)
       .def("count_routes", &AllNodesRouteTable::countRoutes)

@@ -6595,6 +6595,22 @@ __global__ __launch_bounds__(256) void spf_route_select_kernel(RouteSelectArgs a
 // getRouteDelta's (Decision.cpp:47-85) unicast updates + deletes for every
 // node at once.  One wave per 64 prefixes of a row: the ballot of changed
 // lanes is the row's bitmap word; popcounts add up per row.
+//
+// Selected columns (sel_of_b non-null; both tables select the same columns):
+// a cell is also changed when its igp word differs -- bestNexthop.metric of
+// RibUnicastEntry equality is the minimum distance over every reachable
+// candidate, which metric, best and links (the winners' alone) do not show.
+// The words are [row][S], each table's through its own sel_of.  Tables
+// without selected columns run the <false> instance, which has none of this
+// (as spf_route_table_kernel does).
+//
+// ROUTES (spf_route_table_diff_routes, LFA tables): the metric word decides
+// route / no route only; with a route on both sides every link's own metric
+// is compared below and the shortest distance is no part of the route.  An
+// instance of its own too: as a run-time flag the two metric loads no longer
+// short-circuited the best loads and the plain fabric diff measured 12 %
+// slower.
+template <bool SEL, bool ROUTES>
 __global__ __launch_bounds__(256) void spf_route_table_diff_kernel(
     const uint32_t* __restrict__ ma, const uint32_t* __restrict__ ba,
     const uint64_t* __restrict__ la, const uint32_t* __restrict__ mb,
@@ -6602,7 +6618,9 @@ __global__ __launch_bounds__(256) void spf_route_table_diff_kernel(
     const uint64_t* __restrict__ lk_off, uint32_t P, uint32_t nq, uint32_t pw,
     uint64_t* __restrict__ bits, uint32_t* __restrict__ count,
     const uint32_t* __restrict__ lma, const uint32_t* __restrict__ lmb,
-    const uint64_t* __restrict__ lm_off) {
+    const uint64_t* __restrict__ lm_off, const uint32_t* __restrict__ sel_of_a,
+    const uint32_t* __restrict__ sel_of_b, const uint32_t* __restrict__ igp_a,
+    const uint32_t* __restrict__ igp_b, uint32_t Sa, uint32_t Sb) {
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   for (uint32_t q = blockIdx.x; q < nq; q += gridDim.x) {
     const uint32_t WL = P ? (uint32_t)((lk_off[q + 1] - lk_off[q]) / P) : 0;
@@ -6614,7 +6632,19 @@ __global__ __launch_bounds__(256) void spf_route_table_diff_kernel(
       bool ch = false;
       if (p < P) {
         const size_t o = (size_t)q * P + p;
-        ch = ma[o] != mb[o] || ba[o] != bb[o];
+        if constexpr (ROUTES) {
+          ch = (ma[o] == kInf32) != (mb[o] == kInf32) || ba[o] != bb[o];
+        } else {
+          ch = ma[o] != mb[o] || ba[o] != bb[o];
+        }
+        if constexpr (SEL) {
+          if (!ch) {
+            const uint32_t kb = sel_of_b[p];
+            if (kb != kInf32) {
+              ch = igp_a[(size_t)q * Sa + sel_of_a[p]] != igp_b[(size_t)q * Sb + kb];
+            }
+          }
+        }
         for (uint32_t k = 0; k < WL && !ch; ++k) {
           ch = la_q[(size_t)p * WL + k] != lb_q[(size_t)p * WL + k];
         }
@@ -6649,7 +6679,13 @@ __global__ __launch_bounds__(256) void spf_route_table_diff_kernel(
 // mask, and the older mask must have no other bit (link_of is injective, so
 // counting the images against the older popcount decides that).  LFA tables
 // also compare each set link's metric with the metric of its image.  A cell
-// with no route on both sides is unchanged.
+// with no route on both sides is unchanged.  In a column selected in both
+// tables (sel_of_b non-null; the host pairs selected columns with selected
+// ones only) a cell with a route on both sides is also changed when its igp
+// word differs: the older word sits at (row_of[q], older selected index of
+// col_of[p]).  A dirty-list entry kMapNone marks a column whose `best` is no
+// part of the route (a BGP column selected once on the host: its best entry
+// is the column's, not the cell's): best is not compared there.
 //
 // Launch shape of spf_route_table_diff_kernel: one workgroup per row, one
 // wave per 64 columns, the ballot is the bitmap word.  ident[q] != 0 marks a
@@ -6681,6 +6717,10 @@ struct RouteDiffMapArgs {
   const uint32_t* dirty_off;               // [P + 1] or null (no dirty announcers)
   const uint32_t* dirty_ann;
   const uint8_t* ident;                    // [nq] identity-links flag
+  const uint32_t *sel_of_a, *sel_of_b;     // [Pa] / [P] selected index (null: no selected column)
+  const uint32_t *igp_a, *igp_b;           // [rows][Sa] / [rows][Sb]
+  uint32_t Sa, Sb;
+  uint32_t routes_only;
   const uint32_t* deg_b;                   // [nq] up links of the newer row's source
   uint32_t P, Pa, Va, nq, pw, ng, gw;
   uint64_t* bits;                          // [nq * pw]
@@ -6688,6 +6728,16 @@ struct RouteDiffMapArgs {
   uint32_t* count;                         // [nq], zeroed
 };
 
+// SEL: both tables have selected columns; the <false> instance has no igp
+// compare.  (Both instances differ from the kernel before BGP columns in the
+// dirty loop: it runs to its end to find an SPF_MAP_NONE entry.)  The igp
+// compare is a dependent chain of loads (sel_of_b[p], sel_of_a[pa], then the
+// two words) after the first branch, unlike the common-case loads below: it
+// runs only for cells equal so far of tables with selected columns, and no
+// fabric-sized table of that kind has been timed.
+// a.routes_only (spf_route_table_diff_routes, LFA tables): with a route on
+// both sides the metric word is not compared (every link's own metric is).
+template <bool SEL>
 __global__ __launch_bounds__(256) void spf_route_table_diff_mapped_kernel(RouteDiffMapArgs a) {
   __shared__ uint32_t st_link[kRtStage];
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
@@ -6741,10 +6791,22 @@ __global__ __launch_bounds__(256) void spf_route_table_diff_mapped_kernel(RouteD
             ch = ma != mb;
           } else {
             const uint32_t bi = a.node_of ? (ba < a.Va ? a.node_of[ba] : kMapNone) : ba;
-            ch = ma != mb || bi != bb;
-            if (a.dirty_off && !ch) {
-              for (uint32_t i = a.dirty_off[p], e = a.dirty_off[p + 1]; i < e && !ch; ++i) {
-                ch = a.dirty_ann[i] == bb;
+            bool anyBest = false, dirty = false;
+            if (a.dirty_off) {
+              for (uint32_t i = a.dirty_off[p], e = a.dirty_off[p + 1]; i < e; ++i) {
+                const uint32_t d = a.dirty_ann[i];
+                anyBest |= d == kMapNone;
+                dirty |= d == bb;
+              }
+            }
+            ch = (ma != mb && !a.routes_only) || (bi != bb && !anyBest) || dirty;
+            if constexpr (SEL) {
+              if (!ch) {
+                const uint32_t kb = a.sel_of_b[p];
+                if (kb != kMapNone) {
+                  ch = a.igp_a[(size_t)qa * a.Sa + a.sel_of_a[pa]] !=
+                      a.igp_b[(size_t)q * a.Sb + kb];
+                }
               }
             }
             if (ident) {
@@ -6966,6 +7028,11 @@ struct RouteDeltaFillArgs {
   uint32_t P, nq, pw, gw;
   uint32_t *col_out, *metric_out, *best_out, *lmet_out, *gone_out;
   uint64_t* links_out;
+  // tables with selected columns: the igp word of every changed cell
+  // (kInf32 in an unselected column); igp_out null otherwise
+  const uint32_t *sel_of, *sel_igp;
+  uint32_t S;
+  uint32_t* igp_out;
 };
 
 // fn(w, word, rank0) for every non-zero word w of the bitmap row `row`, wave
@@ -7022,6 +7089,10 @@ __global__ __launch_bounds__(kDeltaFillBlock) void spf_route_delta_fill_kernel(
               a.col_out[k0 + r] = p;
               a.metric_out[k0 + r] = a.metric[o];
               a.best_out[k0 + r] = a.best[o];
+              if (a.igp_out) { // uniform over the grid
+                const uint32_t k = a.sel_of[p];
+                a.igp_out[k0 + r] = k != kInf32 ? a.sel_igp[(size_t)q * a.S + k] : kInf32;
+              }
               for (uint32_t j = 0; j < W; ++j) {
                 a.links_out[lw0 + r * W + j] = l_q[(size_t)p * W + j];
               }
@@ -7056,17 +7127,28 @@ __global__ __launch_bounds__(kDeltaFillBlock) void spf_route_delta_fill_kernel(
 
 // Sparse read of a route table (spf_route_table_fetch_cells): cell k =
 // (rows[k], cols[k]); one lane per cell copies metric, best and the row's
-// link words to pos[k] (the host's running sum of link words).
+// link words to pos[k] (the host's running sum of link words).  With igp_out
+// (spf_route_table_fetch_cells_igp, tables with selected columns) the lane
+// copies the cell's igp word, kInf32 in an unselected column; metric_out null
+// then skips the other words.
 __global__ __launch_bounds__(256) void spf_route_cells_gather_kernel(
     const uint32_t* __restrict__ rows, const uint32_t* __restrict__ cols,
     const uint64_t* __restrict__ pos, uint64_t n, uint32_t P,
     const uint32_t* __restrict__ metric, const uint32_t* __restrict__ best,
     const uint64_t* __restrict__ links, const uint64_t* __restrict__ lk_off,
     uint32_t* __restrict__ metric_out, uint32_t* __restrict__ best_out,
-    uint64_t* __restrict__ links_out) {
+    uint64_t* __restrict__ links_out, const uint32_t* __restrict__ sel_of,
+    const uint32_t* __restrict__ sel_igp, uint32_t S, uint32_t* __restrict__ igp_out) {
   for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n;
        k += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t q = rows[k], p = cols[k];
+    if (igp_out) {
+      const uint32_t s = sel_of[p];
+      igp_out[k] = s != kInf32 ? sel_igp[(size_t)q * S + s] : kInf32;
+    }
+    if (!metric_out) {
+      continue;
+    }
     const size_t o = (size_t)q * P + p;
     metric_out[k] = metric[o];
     best_out[k] = best[o];
@@ -14578,6 +14660,7 @@ struct spf_route_table {
   DevBuf<uint32_t> d_count;
   // SPF_RT_LFA
   bool lfa = false;
+  bool diff_routes = false; // spf_route_table_diff_routes
   std::vector<uint64_t> lm_off; // [nq + 1] per-link metric offsets (P * deg)
   DevBuf<uint64_t> d_lm_off;
   DevBuf<uint32_t> d_lmet;
@@ -14604,6 +14687,7 @@ struct spf_route_table {
   // selection kernel
   uint32_t S = 0;
   std::vector<uint32_t> sel_col;
+  std::vector<uint32_t> sel_of; // [P] selected index of a column, kInf32: none (empty: S == 0)
   DevBuf<uint32_t> d_sel_col, d_sel_of, d_sel_w, d_sel_best, d_sel_igp;
   DevBuf<uint64_t> d_pair_off;
   DevBuf<uint16_t> d_pair;
@@ -14798,6 +14882,7 @@ int spf_route_table_create_sel(
   };
   t->S = S;
   t->sel_col.assign(sel->columns, sel->columns + S);
+  t->sel_of = sel_of;
   const uint32_t na = ann_offsets[num_prefixes];
   const size_t cells = (size_t)q->nq * S;
   int st = SPF_OK;
@@ -15050,6 +15135,11 @@ int diff_begin(const spf_route_table* older, spf_route_table* newer, bool mapped
   return SPF_OK;
 }
 
+// column p of `t` is a selected one
+bool is_selected(const spf_route_table* t, uint32_t p) {
+  return t->S && t->sel_of[p] != kInf32;
+}
+
 int diff_finish(spf_route_table* newer, uint32_t* changed) {
   const spf_graph* gb = newer->q->g;
   HIP_TRY(hipMemcpyAsync(changed, newer->d_count, (size_t)newer->q->nq * 4, hipMemcpyDeviceToHost,
@@ -15060,6 +15150,17 @@ int diff_finish(spf_route_table* newer, uint32_t* changed) {
 } // namespace
 
 extern "C" {
+
+int spf_route_table_diff_routes(spf_route_table* t, int on) {
+  if (!t) {
+    return fail(SPF_E_INVALID, "null table");
+  }
+  if (!t->lfa) {
+    return fail(SPF_E_INVALID, "not an LFA table (the cell metric is every next hop's metric)");
+  }
+  t->diff_routes = on != 0;
+  return SPF_OK;
+}
 
 int spf_route_table_diff(spf_route_table* older, spf_route_table* newer, uint32_t* changed) {
   SPF_ABI_RANGE("spf_route_table_diff");
@@ -15074,17 +15175,32 @@ int spf_route_table_diff(spf_route_table* older, spf_route_table* newer, uint32_
     return fail(SPF_E_UNSUPPORTED,
                 "tables differ in rows, prefixes or link layout (rematerialise instead)");
   }
+  for (uint32_t p = 0; (older->S || newer->S) && p < newer->P; ++p) {
+    if (is_selected(older, p) != is_selected(newer, p)) {
+      return fail(SPF_E_UNSUPPORTED, "tables differ in their selected columns (use the maps)");
+    }
+  }
   const uint32_t nq = newer->q->nq, P = newer->P, pw = (P + 63) / 64;
   if (int st = diff_begin(older, newer, false); st != SPF_OK || nq == 0) {
     return st;
   }
   if (P) {
     const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)gb->num_cus * 8);
-    SPF_LAUNCH(spf_route_table_diff_kernel, dim3(grid), dim3(256), 0, gb->stream,
-                       older->d_metric, older->d_best, older->d_links, newer->d_metric,
-                       newer->d_best, newer->d_links, newer->d_lk_off, P, nq, pw,
-                       newer->d_diff, newer->d_count, older->d_lmet, newer->d_lmet,
-                       newer->d_lm_off);
+    auto launch = [&](auto kernel) {
+      SPF_LAUNCH_AS("spf_route_table_diff_kernel", kernel, dim3(grid), dim3(256), 0, gb->stream,
+                    older->d_metric.p, older->d_best.p, older->d_links.p, newer->d_metric.p,
+                    newer->d_best.p, newer->d_links.p,
+                    newer->d_lk_off.p, P, nq, pw, newer->d_diff.p, newer->d_count.p,
+                    older->d_lmet.p, newer->d_lmet.p, newer->d_lm_off.p, older->d_sel_of.p,
+                    newer->d_sel_of.p, older->d_sel_igp.p, newer->d_sel_igp.p, older->S, newer->S);
+    };
+    if (newer->S) {
+      newer->diff_routes ? launch(spf_route_table_diff_kernel<true, true>)
+                         : launch(spf_route_table_diff_kernel<true, false>);
+    } else {
+      newer->diff_routes ? launch(spf_route_table_diff_kernel<false, true>)
+                         : launch(spf_route_table_diff_kernel<false, false>);
+    }
     HIP_TRY(hipGetLastError());
   }
   return diff_finish(newer, changed);
@@ -15150,6 +15266,12 @@ int spf_route_table_diff_mapped(
         return fail(SPF_E_INVALID, "col_of maps two columns to the same older column");
       }
       seen[c] = 1;
+    }
+  }
+  for (uint32_t p = 0; (older->S || newer->S) && p < P; ++p) {
+    const uint32_t c = m.col_of ? m.col_of[p] : p;
+    if (c != SPF_MAP_NONE && is_selected(older, c) != is_selected(newer, p)) {
+      return fail(SPF_E_INVALID, "col_of pairs a selected column with an unselected one");
     }
   }
   if (ng && !m.gone_cols) {
@@ -15232,7 +15354,7 @@ int spf_route_table_diff_mapped(
       return fail(SPF_E_INVALID, "null dirty_ann");
     }
     for (uint32_t i = 0; i < nd; ++i) {
-      if (m.dirty_ann[i] >= Vb) {
+      if (m.dirty_ann[i] != SPF_MAP_NONE && m.dirty_ann[i] >= Vb) {
         return fail(SPF_E_INVALID, "dirty_ann entry out of range");
       }
     }
@@ -15298,8 +15420,21 @@ int spf_route_table_diff_mapped(
     a.bits = newer->d_diff;
     a.gone_bits = newer->d_gone;
     a.count = newer->d_count;
+    a.sel_of_a = older->S ? older->d_sel_of.p : nullptr;
+    a.sel_of_b = newer->S && older->S ? newer->d_sel_of.p : nullptr;
+    a.igp_a = older->d_sel_igp;
+    a.igp_b = newer->d_sel_igp;
+    a.Sa = older->S;
+    a.Sb = newer->S;
+    a.routes_only = newer->diff_routes ? 1u : 0u;
     const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)gb->num_cus * 8);
-    SPF_LAUNCH(spf_route_table_diff_mapped_kernel, dim3(grid), dim3(256), 0, gb->stream, a);
+    if (newer->S && older->S) {
+      SPF_LAUNCH_AS("spf_route_table_diff_mapped_kernel", spf_route_table_diff_mapped_kernel<true>,
+                    dim3(grid), dim3(256), 0, gb->stream, a);
+    } else {
+      SPF_LAUNCH_AS("spf_route_table_diff_mapped_kernel", spf_route_table_diff_mapped_kernel<false>,
+                    dim3(grid), dim3(256), 0, gb->stream, a);
+    }
     HIP_TRY(hipGetLastError());
   }
   return diff_finish(newer, changed);
@@ -15366,7 +15501,7 @@ int spf_route_table_delta_pack(spf_route_table* t, spf_route_delta_sizes* sizes)
     t->pk.link_words = tot[2];
     t->pk.link_metrics = t->lfa ? tot[3] : 0;
     if (t->pk.cells || t->pk.gone) {
-      if (t->d_pk_cell.reserve((size_t)t->pk.cells * 3) != hipSuccess ||
+      if (t->d_pk_cell.reserve((size_t)t->pk.cells * (t->S ? 4 : 3)) != hipSuccess ||
           t->d_pk_links.reserve((size_t)t->pk.link_words) != hipSuccess ||
           t->d_pk_lmet.reserve((size_t)t->pk.link_metrics) != hipSuccess ||
           t->d_pk_gone.reserve((size_t)t->pk.gone) != hipSuccess) {
@@ -15393,6 +15528,10 @@ int spf_route_table_delta_pack(spf_route_table* t, spf_route_delta_sizes* sizes)
       a.links_out = t->d_pk_links;
       a.lmet_out = t->d_pk_lmet;
       a.gone_out = t->d_pk_gone;
+      a.sel_of = t->d_sel_of;
+      a.sel_igp = t->d_sel_igp;
+      a.S = t->S;
+      a.igp_out = t->S ? t->d_pk_cell + 3 * t->pk.cells : nullptr;
       const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)g->num_cus * 8);
       SPF_LAUNCH(spf_route_delta_fill_kernel, dim3(grid), dim3(kDeltaFillBlock), 0, g->stream, a);
       HIP_TRY(hipGetLastError());
@@ -15445,12 +15584,45 @@ int spf_route_table_delta_fetch(
   return SPF_OK;
 }
 
-int spf_route_table_fetch_cells(
-    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* metric,
-    uint32_t* best, uint64_t* links, uint32_t* link_metrics) {
-  SPF_ABI_RANGE("spf_route_table_fetch_cells");
+int spf_route_table_delta_fetch_igp(spf_route_table* t, uint32_t* igp) {
+  SPF_ABI_RANGE("spf_route_table_delta_fetch_igp");
   if (!t) {
     return fail(SPF_E_INVALID, "null table");
+  }
+  if (!t->S) {
+    return fail(SPF_E_UNSUPPORTED, "the table has no selected columns (no igp lane)");
+  }
+  if (!t->packed) {
+    return fail(SPF_E_INVALID, "no delta has been packed on this table");
+  }
+  if (t->pk_epoch != t->epoch) {
+    return fail(SPF_E_INVALID, "the packed delta is stale (the table ran or diffed since)");
+  }
+  if (!t->pk.cells) {
+    return SPF_OK;
+  }
+  if (!igp) {
+    return fail(SPF_E_INVALID, "null output for a non-empty list");
+  }
+  spf_graph* g = t->q->g;
+  HIP_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemcpy(igp, t->d_pk_cell + 3 * t->pk.cells, t->pk.cells * 4, hipMemcpyDeviceToHost));
+  return SPF_OK;
+}
+
+} // extern "C"
+
+namespace {
+// spf_route_table_fetch_cells (igp null) and _fetch_cells_igp (igp alone)
+int fetch_cells_impl(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* metric,
+    uint32_t* best, uint64_t* links, uint32_t* link_metrics, uint32_t* igp_out, bool igp) {
+  if (!t) {
+    return fail(SPF_E_INVALID, "null table");
+  }
+  if (igp && !t->S) {
+    return fail(SPF_E_UNSUPPORTED, "the table has no selected columns (no igp word)");
   }
   if (!t->ran) {
     return fail(SPF_E_INVALID, "table has not run");
@@ -15458,16 +15630,19 @@ int spf_route_table_fetch_cells(
   if (n == 0) {
     return SPF_OK;
   }
-  if (!rows || !cols || !metric || !best) {
+  if (!rows || !cols || (igp ? !igp_out : (!metric || !best))) {
     return fail(SPF_E_INVALID, "null argument");
   }
   // ---- validation (host): every index the kernels follow is in range
   const uint32_t nq = t->q->nq, P = t->P;
-  std::vector<uint64_t> pos(t->lfa ? 2 * n : n);
+  std::vector<uint64_t> pos(igp ? 0 : t->lfa ? 2 * n : n);
   uint64_t nl = 0, nm = 0;
   for (uint64_t k = 0; k < n; ++k) {
     if (rows[k] >= nq || cols[k] >= P) {
       return fail(SPF_E_INVALID, "cell row or column out of range");
+    }
+    if (igp) {
+      continue; // one word per cell: no link positions
     }
     pos[k] = nl;
     nl += (t->lk_off[rows[k] + 1] - t->lk_off[rows[k]]) / P;
@@ -15483,7 +15658,7 @@ int spf_route_table_fetch_cells(
   HIP_TRY(hipSetDevice(g->device));
   if (t->d_gc_idx.reserve((size_t)n * 2) != hipSuccess ||
       t->d_gc_pos.reserve(pos.size()) != hipSuccess ||
-      t->d_gc_out.reserve((size_t)n * 2) != hipSuccess ||
+      t->d_gc_out.reserve((size_t)n * 3) != hipSuccess ||
       t->d_gc_links.reserve((size_t)nl) != hipSuccess ||
       t->d_gc_lmet.reserve((size_t)nm) != hipSuccess) {
     return fail(SPF_E_NOMEM, "route delta buffer");
@@ -15492,14 +15667,23 @@ int spf_route_table_fetch_cells(
   // landed (stream order, then the final synchronise) before this one returns
   HIP_TRY(hipMemcpyAsync(t->d_gc_idx, rows, n * 4, hipMemcpyHostToDevice, g->stream));
   HIP_TRY(hipMemcpyAsync(t->d_gc_idx + n, cols, n * 4, hipMemcpyHostToDevice, g->stream));
-  HIP_TRY(hipMemcpyAsync(t->d_gc_pos, pos.data(), pos.size() * 8, hipMemcpyHostToDevice,
-                         g->stream));
+  if (!pos.empty()) {
+    HIP_TRY(hipMemcpyAsync(t->d_gc_pos, pos.data(), pos.size() * 8, hipMemcpyHostToDevice,
+                           g->stream));
+  }
   const uint32_t maxGrid = (uint32_t)g->num_cus * 8;
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, maxGrid);
   SPF_LAUNCH(spf_route_cells_gather_kernel, dim3(grid), dim3(256), 0, g->stream, t->d_gc_idx,
              t->d_gc_idx + n, t->d_gc_pos, n, P, t->d_metric, t->d_best, t->d_links, t->d_lk_off,
-             t->d_gc_out, t->d_gc_out + n, t->d_gc_links);
+             igp ? nullptr : t->d_gc_out.p, t->d_gc_out + n, t->d_gc_links, t->d_sel_of,
+             t->d_sel_igp, t->S, igp ? t->d_gc_out + 2 * n : nullptr);
   HIP_TRY(hipGetLastError());
+  if (igp) {
+    HIP_TRY(hipMemcpyAsync(igp_out, t->d_gc_out + 2 * n, n * 4, hipMemcpyDeviceToHost,
+                           g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return SPF_OK;
+  }
   if (nm) {
     const uint32_t wgrid = (uint32_t)std::min<uint64_t>((n + 3) / 4, maxGrid);
     SPF_LAUNCH(spf_route_cells_gather_lmet_kernel, dim3(wgrid), dim3(256), 0, g->stream,
@@ -15517,6 +15701,22 @@ int spf_route_table_fetch_cells(
   }
   HIP_TRY(hipStreamSynchronize(g->stream));
   return SPF_OK;
+}
+} // namespace
+
+extern "C" {
+
+int spf_route_table_fetch_cells(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* metric,
+    uint32_t* best, uint64_t* links, uint32_t* link_metrics) {
+  SPF_ABI_RANGE("spf_route_table_fetch_cells");
+  return fetch_cells_impl(t, n, rows, cols, metric, best, links, link_metrics, nullptr, false);
+}
+
+int spf_route_table_fetch_cells_igp(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* igp) {
+  SPF_ABI_RANGE("spf_route_table_fetch_cells_igp");
+  return fetch_cells_impl(t, n, rows, cols, nullptr, nullptr, nullptr, nullptr, igp, true);
 }
 
 } // extern "C"
