@@ -563,6 +563,50 @@ int spf_route_table_diff_mapped(
  * row had a route in gone_cols[g]; bits[ceil(num_gone/64)]. */
 int spf_route_table_changed_gone(spf_route_table* t, uint32_t i, uint64_t* bits);
 
+/* A prefix change in place (PrefixState::updatePrefixDatabase's changed set:
+ * the graph, the query's rows and the next-hop masks are as they were): the
+ * listed columns of a table that has run get new announcer lists and
+ * spf_route_patch_kernel recomputes their cells from the resident SPF rows,
+ * comparing each with the cell it replaces in the same pass. */
+typedef struct spf_route_patch {
+  uint32_t num_columns;
+  const uint32_t* columns;     /* [num_columns] distinct column indices < P */
+  const uint32_t* ann_offsets; /* [num_columns + 1], starts at 0, monotone */
+  const uint32_t* announcers;  /* node ids: the NEW announcer list of columns[k] */
+  const uint32_t* dirty_off;   /* [num_columns + 1] or NULL (no dirty announcers) */
+  const uint32_t* dirty_ann;   /* node ids, same meaning as spf_route_diff_map::dirty_ann */
+} spf_route_patch;
+/* After the call every cell of `t` is bit-equal to the cell of a table freshly
+ * created over the same query with the patched announcer lists and run
+ * (metric, best, link words and, SPF_RT_LFA, link metrics); columns not listed
+ * are not touched.  The resident announcer arrays are replaced too: a later
+ * spf_route_table_run on `t` reproduces the patched cells.
+ * The changed bitmap of `t` becomes what spf_route_table_diff_mapped(before,
+ * after, map) reports with all-identity maps and the given dirty lists: cell
+ * (i, c) is set iff exactly one side has a route, or both have one and the
+ * metric, the best announcer, the link words or (SPF_RT_LFA) a link metric
+ * differs, or the new best is a dirty announcer of the column
+ * (spf_route_table_diff_routes is honoured); bits of unlisted columns are
+ * clear; changed[i] (NULL: not wanted) = the popcount of row i.  `t` is left as
+ * after an equal-layout diff: the epoch moved (an earlier pack is stale),
+ * spf_route_table_changed, _delta_pack, _delta_fetch and _fetch_cells work,
+ * _changed_gone reports no gone columns, and a second patch replaces the
+ * first one's bitmap.  num_columns == 0 is SPF_OK with an all-clear bitmap.
+ * Everything is checked on the host first; on an error the table, its bitmap
+ * and its pack state are as before the call.  SPF_E_INVALID: a null argument,
+ * a table that has not run, a column >= P or listed twice, an announcer or
+ * dirty id >= V (SPF_MAP_NONE included), offsets that do not start at 0 or
+ * decrease.  SPF_E_UNSUPPORTED: a listed column that is a selected one (its
+ * pair tables would have to be replaced: recreate the table).
+ * Earlier work on the graph's stream (spf_route_table_run is asynchronous)
+ * ends before the old announcer arrays are released; the call returns after
+ * the patch.  The scratch cells it keeps are num_columns / P of the table's. */
+int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
+                                  uint32_t* changed /*[rows] or NULL*/);
+/* Device time of the last spf_route_table_patch_columns (clearing the bitmap
+ * and spf_route_patch_kernel). */
+int spf_route_table_patch_elapsed_ms(spf_route_table* t, float* ms);
+
 /* The delta itself (getRouteDelta, Decision.cpp:47-85: the updates and
  * deletes, not their number) of every node as one record list built on the
  * device: the changed cells of the last diff, compacted out of the bitmaps,

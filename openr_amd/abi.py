@@ -102,6 +102,8 @@ EXPORTED_SYMBOLS = (
     "spf_route_table_delta_fetch_igp",
     "spf_route_table_fetch_cells_igp",
     "spf_route_table_diff_routes",
+    "spf_route_table_patch_columns",
+    "spf_route_table_patch_elapsed_ms",
     "spf_cluster_unique_id",
     "spf_cluster_create_local",
     "spf_cluster_create_rank",
@@ -263,6 +265,17 @@ class _RouteSelectDesc(C.Structure):
     ]
 
 
+class _RoutePatch(C.Structure):
+    _fields_ = [
+        ("num_columns", C.c_uint32),
+        ("columns", C.POINTER(C.c_uint32)),
+        ("ann_offsets", C.POINTER(C.c_uint32)),
+        ("announcers", C.POINTER(C.c_uint32)),
+        ("dirty_off", C.POINTER(C.c_uint32)),
+        ("dirty_ann", C.POINTER(C.c_uint32)),
+    ]
+
+
 class _RouteDeltaSizes(C.Structure):
     _fields_ = [
         ("cells", C.c_uint64),
@@ -281,6 +294,31 @@ def _route_diff_map(row_of=None, col_of=None, gone_cols=None, node_of=None, link
     ptr = [None if x is None or len(x) == 0 else _p(x, C.c_uint32) for x in keep]
     m = _RouteDiffMap(*ptr, 0 if keep[2] is None else len(keep[2]))
     return m, keep
+
+
+def _route_patch(columns, announcers, dirty=None):
+    """(spf_route_patch, arrays it points into): announcers[k] is the new
+    list of columns[k], dirty[k] (dirty None: a null dirty_off) its dirty
+    announcers."""
+    cols = np.ascontiguousarray(columns, dtype=np.uint32)
+    k = len(cols)
+    assert len(announcers) == k and (dirty is None or len(dirty) == k)
+
+    def csr(lists):
+        off = np.zeros(k + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(a) for a in lists])
+        flat = [int(x) for a in lists for x in a]
+        return off, np.asarray(flat if flat else [0], dtype=np.uint32)
+
+    off, ann = csr(announcers)
+    keep = [cols if k else np.zeros(1, dtype=np.uint32), off, ann]
+    ptr = [_p(x, C.c_uint32) for x in keep]
+    if dirty is None:
+        ptr += [None, None]
+    else:
+        keep += list(csr(dirty))
+        ptr += [_p(x, C.c_uint32) for x in keep[3:]]
+    return _RoutePatch(k, *ptr), keep
 
 
 _lib = None
@@ -426,6 +464,8 @@ def load():
                                                   pu32]),
         "spf_route_table_delta_fetch_igp": (C.c_int, [vp, pu32]),
         "spf_route_table_diff_routes": (C.c_int, [vp, C.c_int]),
+        "spf_route_table_patch_columns": (C.c_int, [vp, C.POINTER(_RoutePatch), pu32]),
+        "spf_route_table_patch_elapsed_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "spf_route_table_fetch_cells_igp": (C.c_int, [vp, C.c_uint64, pu32, pu32, pu32]),
     }
     for name, (res, args) in sig.items():
@@ -1129,6 +1169,26 @@ class RouteTable:
             _p(metric, C.c_uint32), _p(best, C.c_uint32), _p(links, C.c_uint64),
             _p(lmet, C.c_uint32) if self.lfa else None), "spf_route_table_fetch_cells")
         return metric[:n], best[:n], links[:nl], lmet[:nm]
+
+    def patch_columns(self, columns, announcers, dirty=None) -> np.ndarray:
+        """spf_route_table_patch_columns: column columns[k] gets the announcer
+        list announcers[k] (dirty[k]: its dirty announcers), in place; returns
+        the changed columns per row.  The table is left as after an
+        equal-layout diff (changed, delta_pack, fetch_cells)."""
+        m, keep = _route_patch(columns, announcers, dirty)
+        out = np.zeros(max(self.n, 1), dtype=np.uint32)
+        _check(load().spf_route_table_patch_columns(self.h, C.byref(m), _p(out, C.c_uint32)),
+               "spf_route_table_patch_columns")
+        self.num_gone = 0
+        del keep
+        return out[: self.n]
+
+    def patch_ms(self) -> float:
+        """Device time of the last patch_columns."""
+        ms = C.c_float()
+        _check(load().spf_route_table_patch_elapsed_ms(self.h, C.byref(ms)),
+               "spf_route_table_patch_elapsed_ms")
+        return float(ms.value)
 
     def diff_routes(self, on: bool = True):
         """spf_route_table_diff_routes (SPF_RT_LFA tables): later diffs into

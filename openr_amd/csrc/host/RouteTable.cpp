@@ -41,7 +41,6 @@ void forEachSetBit(const uint64_t* words, size_t n, F&& f) {
 // selectEcmpOpenr, and with bgpColumns selectEcmpBgp): read-only PrefixState
 // lookups, one prefix per call on the host pool
 void AllNodesRouteTable::scanPrefix(PrefixScan& s, size_t i) const {
-  const LinkState& ls = s.ls;
   const PrefixState& ps = s.ps;
   const auto* borderNodes = s.borderNodes;
   const bool bgpColumns = s.bgpColumns, bgpUseIgpMetric = s.bgpUseIgpMetric;
@@ -186,7 +185,7 @@ void AllNodesRouteTable::scanPrefix(PrefixScan& s, size_t i) const {
     // maybeFilterDrainedNodes (Decision.cpp:651-666)
     std::set<std::string> undrained;
     for (const auto& w : winners) {
-      if (!ls.isNodeOverloaded(w)) {
+      if (!s.ls->isNodeOverloaded(w)) {
         undrained.insert(w);
       }
     }
@@ -357,7 +356,7 @@ void AllNodesRouteTable::createAndRunTable(
   int s = SPF_OK;
   spf_route_table* table = nullptr;
   if ((s = spf_route_table_create_sel(
-           query_.get(), (uint32_t)(prefixes_.size() + owners_.size()), annOff.data(),
+           query_.get(), (uint32_t)numCols(), annOff.data(),
            ann.empty() ? nullptr : ann.data(), lfa_ ? SPF_RT_LFA : 0u, nsel_ ? &sd : nullptr,
            &table)) != SPF_OK) {
     tableFailure("spf_route_table_create", s);
@@ -387,13 +386,15 @@ void AllNodesRouteTable::createAndRunTable(
 AllNodesRouteTable::AllNodesRouteTable(
     const LinkState& ls, const PrefixState& ps, bool enableV4, bool computeLfa,
     const std::unordered_set<std::string>* borderNodes, bool bgpColumns, bool bgpDryRun,
-    bool bgpUseIgpMetric)
+    bool bgpUseIgpMetric, size_t spareColumns)
     : area_(ls.getArea()),
       enableV4_(enableV4),
       lfa_(computeLfa),
       bgpColumns_(bgpColumns),
       bgpDryRun_(bgpDryRun),
-      bgpIgp_(bgpUseIgpMetric) {
+      bgpIgp_(bgpUseIgpMetric),
+      spare_(spareColumns),
+      hasBorder_(borderNodes != nullptr) {
   auto tp = std::chrono::steady_clock::now();
   LinkState::Engine& eng = ls.engine();
   Counters::add("decision.route_table_engine_us", usSince(tp));
@@ -452,7 +453,7 @@ AllNodesRouteTable::AllNodesRouteTable(
   std::vector<uint32_t> annOff{0}, ann;
   {
     // eligible prefixes with their announcers, kept in the map's iteration order
-    PrefixScan scan{ls, ps, borderNodes, bgpColumns, bgpUseIgpMetric};
+    PrefixScan scan{&ls, ps, borderNodes, bgpColumns, bgpUseIgpMetric};
     scan.items.reserve(ps.prefixes().size());
     for (const auto& [prefix, entries] : ps.prefixes()) {
       scan.items.emplace_back(&prefix, &entries);
@@ -479,6 +480,18 @@ AllNodesRouteTable::AllNodesRouteTable(
   Counters::add("decision.route_table_prefixes_us", usSince(tp));
   addNodeLabelColumns(ls, annOff, ann);
   Counters::add("decision.route_table_labels_us", usSince(tp));
+  if (spare_) {
+    // spare columns: empty lists after the label columns, all free
+    annOff.insert(annOff.end(), spare_, (uint32_t)ann.size());
+    sparePrefix_.resize(spare_);
+    spareAnn_.resize(spare_);
+    free_.assign(prefixes_.size() + spare_, 0);
+    for (size_t j = spare_; j-- > 0;) {
+      free_[prefixes_.size() + j] = 1;
+      freeList_.push_back((uint32_t)(spareBase() + j)); // (taken from the back: ascending)
+    }
+    rebuildServed();
+  }
   collectAdjLabels(ls);
   Counters::add("decision.route_table_host_us", usSince(tp)); // (from the same start)
   createAndRunTable(annOff, ann);
@@ -495,7 +508,7 @@ AllNodesRouteTable::~AllNodesRouteTable() {
 
 uint64_t AllNodesRouteTable::countRoutes() const {
   uint64_t n = 0;
-  const size_t C = prefixes_.size() + owners_.size();
+  const size_t C = numCols();
   std::vector<uint32_t> metric(C), best(C);
   std::vector<uint64_t> links;
   for (uint32_t i = 0; i < names_.size(); ++i) {
@@ -505,8 +518,8 @@ uint64_t AllNodesRouteTable::countRoutes() const {
         s != SPF_OK) {
       tableFailure("spf_route_table_fetch", s);
     }
-    for (size_t p = 0; p < prefixes_.size(); ++p) {
-      n += metric[p] != 0xFFFFFFFFu;
+    for (size_t p = 0; p < C; ++p) {
+      n += isUni(p) && metric[p] != 0xFFFFFFFFu;
     }
   }
   return n;
@@ -518,7 +531,7 @@ AllNodesRouteTable::Row AllNodesRouteTable::fetchRow(uint32_t i) const {
   if (w < 0) {
     tableFailure("spf_route_table_link_words", w);
   }
-  const size_t P = prefixes_.size() + owners_.size();
+  const size_t P = numCols();
   r.W = (size_t)w;
   r.metric.resize(P);
   r.best.resize(P);
@@ -559,13 +572,13 @@ std::unordered_set<thrift::NextHopThrift> AllNodesRouteTable::cellNextHops(
 
 RibUnicastEntry AllNodesRouteTable::materialise(
     const std::string& node, uint32_t i, const Row& r, size_t p) const {
-  const bool isV4 = prefixes_[p].prefixAddress.addr.size() == 4;
+  const bool isV4 = prefixAt(p).prefixAddress.addr.size() == 4;
   auto nhs = cellNextHops(i, r, p, [&](const Link& l, int32_t metric) {
     return createNextHop(
         isV4 ? l.getNhV4FromNode(node) : l.getNhV6FromNode(node), l.getIfaceFromNode(node),
         metric, std::nullopt, false, l.getArea());
   });
-  if (sel_[p]) {
+  if (columnKind(p) == 2) {
     // selectEcmpBgp (Decision.cpp:805-866) per node: the cell's best
     // candidate, its loopback with the cell's igp as metric
     // (PrefixState.cpp:111-126)
@@ -580,14 +593,14 @@ RibUnicastEntry AllNodesRouteTable::materialise(
     }
     throw std::logic_error("AllNodesRouteTable: best candidate not in the selected column");
   }
-  if (bgp_[p]) {
+  if (columnKind(p) == 1) {
     // selectEcmpBgp (Decision.cpp:805-866): the host-side selection's best
     const BgpSel& b = *bgp_[p];
     return RibUnicastEntry(prefixes_[p], std::move(nhs), b.bestEntry, b.bestArea, bgpDryRun_,
                            b.bestNexthop);
   }
   const thrift::PrefixEntry* bestEntry = nullptr;
-  for (const auto& a : announcers_[p]) {
+  for (const auto& a : annsAt(p)) {
     if (a.id == r.bestOf(p)) {
       bestEntry = &a.entry;
     }
@@ -595,20 +608,20 @@ RibUnicastEntry AllNodesRouteTable::materialise(
   if (!bestEntry) {
     throw std::logic_error("AllNodesRouteTable: best announcer not in the prefix");
   }
-  return RibUnicastEntry(prefixes_[p], std::move(nhs), *bestEntry, area_);
+  return RibUnicastEntry(prefixAt(p), std::move(nhs), *bestEntry, area_);
 }
 
 std::unordered_map<thrift::IpPrefix, RibUnicastEntry> AllNodesRouteTable::routes(
     const std::string& node) const {
   std::unordered_map<thrift::IpPrefix, RibUnicastEntry> out;
   auto it = ids_.find(node);
-  if (it == ids_.end() || prefixes_.empty()) {
+  if (it == ids_.end() || (prefixes_.empty() && !spare_)) {
     return out;
   }
   const Row r = fetchRow(it->second);
-  for (size_t p = 0; p < prefixes_.size(); ++p) {
-    if (r.metricOf(p) != 0xFFFFFFFFu) {
-      out.emplace(prefixes_[p], materialise(node, it->second, r, p));
+  for (size_t p = 0; p < numCols(); ++p) {
+    if (isUni(p) && r.metricOf(p) != 0xFFFFFFFFu) {
+      out.emplace(prefixAt(p), materialise(node, it->second, r, p));
     }
   }
   return out;
@@ -708,8 +721,9 @@ std::vector<uint32_t> AllNodesRouteTable::diff(const AllNodesRouteTable& older) 
     throw std::invalid_argument(
         "AllNodesRouteTable::diff: different bgpColumns, bgpDryRun or bgpUseIgpMetric");
   }
-  if (older.names_ != names_ || older.prefixes_ != prefixes_ || older.row_ != row_ ||
-      !sameOwners) {
+  // spare or freed columns: unicast columns pair by prefix, a free one with none
+  if (older.names_ != names_ || holes_ || older.holes_ || older.prefixes_ != prefixes_ ||
+      older.row_ != row_ || !sameOwners) {
     return diffMapped(older);
   }
   // a changed PrefixEntry of a kept announcer changes routes whose cells are
@@ -762,13 +776,14 @@ std::vector<uint32_t> AllNodesRouteTable::diff(const AllNodesRouteTable& older) 
     rowOf_[i] = i;
   }
   older_ = &older;
+  patchDelta_ = false;
   return changed;
 }
 
 std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& older) {
   const uint32_t V = (uint32_t)names_.size(), Va = (uint32_t)older.names_.size();
-  const size_t P = prefixes_.size(), C = P + owners_.size();
-  const size_t Pa = older.prefixes_.size(), Ca = Pa + older.owners_.size();
+  const size_t P = prefixes_.size(), C = numCols();
+  const size_t Pa = older.prefixes_.size(), Ca = older.numCols();
   // rows and best announcers: by node name
   std::vector<uint32_t> rowOf(V, SPF_MAP_NONE), nodeOf(Va, SPF_MAP_NONE);
   for (uint32_t i = 0; i < V; ++i) {
@@ -785,11 +800,17 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
   {
     std::unordered_map<thrift::IpPrefix, uint32_t> colA;
     colA.reserve(Pa);
-    for (uint32_t p = 0; p < Pa; ++p) {
-      colA.emplace(older.prefixes_[p], p);
+    // (a free column serves no prefix: no counterpart, and no route on either side)
+    for (uint32_t p = 0; p < Ca; ++p) {
+      if (older.isUni(p) && !older.isFree(p)) {
+        colA.emplace(older.prefixAt(p), p);
+      }
     }
-    for (size_t p = 0; p < P; ++p) {
-      auto it = colA.find(prefixes_[p]);
+    for (size_t p = 0; p < C; ++p) {
+      if (!isUni(p) || isFree(p)) {
+        continue;
+      }
+      auto it = colA.find(prefixAt(p));
       if (it == colA.end()) {
         continue;
       }
@@ -881,24 +902,41 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
   // is dirty when its entry or its loopback differs.
   std::vector<uint32_t> dirtyOff(C + 1, 0), dirtyAnn;
   for (size_t p = 0; p < C; ++p) {
-    if (p < P && colOf[p] != SPF_MAP_NONE) {
+    if (isUni(p) && colOf[p] != SPF_MAP_NONE) {
       const uint32_t pa = colOf[p];
-      const auto& olds = older.announcers_[pa];
-      if (bgp_[p]) {
+      const auto& olds = older.annsAt(pa);
+      const auto& news = annsAt(p);
+      if (columnKind(p) == 1) {
         dirtyAnn.push_back(SPF_MAP_NONE);
         if (!sameSelection(*bgp_[p], *older.bgp_[pa])) {
-          for (const auto& a : announcers_[p]) {
+          for (const auto& a : news) {
+            dirtyAnn.push_back(a.id);
+          }
+        }
+      } else if (columnKind(p) == 0 && !olds.empty() && !news.empty() &&
+                 !(olds.size() == 1 && news.size() == 1 && nodeOf[olds[0].id] == news[0].id) &&
+                 std::all_of(olds.begin(), olds.end(), [&](const Announcer& o) {
+                   return o.entry == olds[0].entry;
+                 })) {
+        // several announcers (or another one) with ONE PrefixEntry on the
+        // older side: bestPrefixEntry was that entry whoever was best, so a
+        // route's entry changed iff the newer best's differs from it -- not
+        // when `best` moves between equal entries (an anycast gaining an
+        // announcer).  The cell's best is not compared (SPF_MAP_NONE).
+        dirtyAnn.push_back(SPF_MAP_NONE);
+        for (const auto& a : news) {
+          if (!(a.entry == olds[0].entry)) {
             dirtyAnn.push_back(a.id);
           }
         }
       } else {
-        for (size_t c = 0; c < announcers_[p].size(); ++c) {
-          const auto& a = announcers_[p][c];
+        for (size_t c = 0; c < news.size(); ++c) {
+          const auto& a = news[c];
           for (size_t b = 0; b < olds.size(); ++b) {
             const auto& o = olds[b];
             if (nodeOf[o.id] == a.id &&
                 (!(o.entry == a.entry) ||
-                 (sel_[p] && !(sel_[p]->via[c] == older.sel_[pa]->via[b])))) {
+                 (columnKind(p) == 2 && !(sel_[p]->via[c] == older.sel_[pa]->via[b])))) {
               dirtyAnn.push_back(a.id);
             }
           }
@@ -986,7 +1024,245 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
   goneCols_ = std::move(gone);
   goneNew_ = std::move(goneNew);
   older_ = &older;
+  patchDelta_ = false;
   return changed;
+}
+
+// prefixes() once the columns have holes: the served unicast columns in
+// column order, and their index by prefix
+void AllNodesRouteTable::rebuildServed() {
+  holes_ = true;
+  if (free_.empty()) {
+    free_.assign(prefixes_.size() + spare_, 0);
+  }
+  served_.clear();
+  colOfPrefix_.clear();
+  for (size_t c = 0; c < numCols(); ++c) {
+    if (isUni(c) && !isFree(c)) {
+      served_.push_back(prefixAt(c));
+      colOfPrefix_.emplace(prefixAt(c), (uint32_t)c);
+    }
+  }
+}
+
+std::vector<uint32_t> AllNodesRouteTable::applyPrefixChanges(
+    const PrefixState& ps, const std::unordered_set<thrift::IpPrefix>& changed) {
+  if (bgpColumns_ || hasBorder_) {
+    throw std::invalid_argument(
+        "AllNodesRouteTable::applyPrefixChanges: tables with bgpColumns or borderNodes are "
+        "rebuilt (BGP columns and per-area served sets do not move in place)");
+  }
+  const auto tp = std::chrono::steady_clock::now();
+  if (!holes_) {
+    rebuildServed(); // (the index by prefix; no column is free yet)
+  }
+  // rescan every changed prefix with the constructor's rules
+  static const thrift::PrefixEntries kNoEntries;
+  PrefixScan scan{nullptr, ps, nullptr, false, bgpIgp_};
+  for (const auto& prefix : changed) {
+    auto it = ps.prefixes().find(prefix);
+    scan.items.emplace_back(&prefix, it == ps.prefixes().end() ? &kNoEntries : &it->second);
+  }
+  const size_t n = scan.items.size();
+  scan.keep.assign(n, 0);
+  scan.anns.resize(n);
+  scan.sels.resize(n);
+  scan.selCols.resize(n);
+  scan.bgpAll.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    scanPrefix(scan, i);
+  }
+  // classify; nothing is touched before every new prefix has a column
+  std::vector<uint32_t> colFor(n, SPF_MAP_NONE);
+  size_t need = 0;
+  for (size_t i = 0; i < n; ++i) {
+    auto it = colOfPrefix_.find(*scan.items[i].first);
+    if (it != colOfPrefix_.end()) {
+      colFor[i] = it->second;
+    } else {
+      need += scan.keep[i] != 0;
+    }
+  }
+  if (need > freeList_.size()) {
+    throw std::length_error(
+        "AllNodesRouteTable::applyPrefixChanges: " + std::to_string(need) +
+        " new prefixes, " + std::to_string(freeList_.size()) + " free columns (rebuild the table)");
+  }
+  std::vector<uint32_t> cols, annOff{0}, ann, dirtyOff{0}, dirtyAnn;
+  std::vector<size_t> item; // per listed column: its changed prefix
+  for (size_t i = 0; i < n; ++i) {
+    if (colFor[i] == SPF_MAP_NONE) {
+      if (!scan.keep[i]) {
+        continue; // not served before or now
+      }
+      colFor[i] = freeList_.back(); // (freed columns lie behind the spare ones: reused first)
+      freeList_.pop_back();
+    } else {
+      // kept announcers whose PrefixEntry differs (the rule of diffMapped)
+      for (const auto& a : scan.anns[i]) {
+        for (const auto& o : annsAt(colFor[i])) {
+          if (o.id == a.id && !(o.entry == a.entry)) {
+            dirtyAnn.push_back(a.id);
+          }
+        }
+      }
+    }
+    cols.push_back(colFor[i]);
+    item.push_back(i);
+    for (const auto& a : scan.anns[i]) { // (empty when the prefix is no longer served)
+      ann.push_back(a.id);
+    }
+    annOff.push_back((uint32_t)ann.size());
+    dirtyOff.push_back((uint32_t)dirtyAnn.size());
+  }
+  // A kept column whose announcer set changed: `best` can move between two
+  // announcers with EQUAL PrefixEntries, which the device reports (best is a
+  // cell word) and getRouteDelta does not (bestPrefixEntry is the same).  The
+  // cells of those columns are read before and after the patch and such
+  // cells taken out of this call's delta (suppress_).
+  const uint32_t V = (uint32_t)names_.size();
+  std::vector<size_t> risk; // indices into cols
+  std::vector<std::vector<Announcer>> riskOld;
+  for (size_t k = 0; k < cols.size(); ++k) {
+    const auto& olds = annsAt(cols[k]);
+    const auto& news = scan.anns[item[k]];
+    if (isFree(cols[k]) || news.empty() || olds.empty()) {
+      continue;
+    }
+    bool sameIds = olds.size() == news.size();
+    for (size_t c = 0; sameIds && c < news.size(); ++c) {
+      sameIds = olds[c].id == news[c].id;
+    }
+    if (!sameIds) {
+      risk.push_back(k);
+      riskOld.push_back(olds);
+    }
+  }
+  struct CellList {
+    std::vector<uint32_t> metric, best, lmet;
+    std::vector<uint64_t> links;
+  };
+  std::vector<uint32_t> riskRows, riskCols;
+  uint64_t riskLw = 0, riskLm = 0;
+  for (uint32_t i = 0; !risk.empty() && i < V; ++i) {
+    const uint64_t deg = row_[i + 1] - row_[i];
+    for (const size_t k : risk) {
+      riskRows.push_back(i);
+      riskCols.push_back(cols[k]);
+      riskLw += (deg + 63) / 64;
+      riskLm += lfa_ ? deg : 0;
+    }
+  }
+  auto readRisk = [&]() {
+    CellList c;
+    c.metric.resize(riskRows.size());
+    c.best.resize(riskRows.size());
+    c.links.resize(std::max<uint64_t>(riskLw, 1));
+    c.lmet.resize(std::max<uint64_t>(riskLm, 1));
+    if (int s = spf_route_table_fetch_cells(
+            table_.get(), riskRows.size(), riskRows.data(), riskCols.data(), c.metric.data(),
+            c.best.data(), c.links.data(), lfa_ ? c.lmet.data() : nullptr);
+        s != SPF_OK) {
+      tableFailure("spf_route_table_fetch_cells", s);
+    }
+    return c;
+  };
+  const CellList riskBefore = risk.empty() ? CellList{} : readRisk();
+  spf_route_patch patch{};
+  patch.num_columns = (uint32_t)cols.size();
+  patch.columns = cols.data();
+  patch.ann_offsets = annOff.data();
+  patch.announcers = ann.data();
+  patch.dirty_off = dirtyAnn.empty() ? nullptr : dirtyOff.data();
+  patch.dirty_ann = dirtyAnn.data();
+  std::vector<uint32_t> counts(names_.size());
+  if (int s = spf_route_table_patch_columns(table_.get(), &patch, counts.data()); s != SPF_OK) {
+    // (the engine checked before it touched anything: give the columns back)
+    for (size_t k = cols.size(); k-- > 0;) {
+      if (isFree(cols[k])) {
+        freeList_.push_back(cols[k]);
+      }
+    }
+    tableFailure("spf_route_table_patch_columns", s);
+  }
+  if (int s = spf_route_table_patch_elapsed_ms(table_.get(), &patchMs_); s != SPF_OK) {
+    tableFailure("spf_route_table_patch_elapsed_ms", s);
+  }
+  suppress_.assign(V, {});
+  if (!risk.empty()) {
+    const CellList after = readRisk();
+    auto entryOf = [](const std::vector<Announcer>& as, uint32_t id) -> const thrift::PrefixEntry* {
+      for (const auto& a : as) {
+        if (a.id == id) {
+          return &a.entry;
+        }
+      }
+      return nullptr;
+    };
+    size_t x = 0;
+    uint64_t lw = 0, lm = 0;
+    for (uint32_t i = 0; i < V; ++i) {
+      const uint64_t deg = row_[i + 1] - row_[i], W = (deg + 63) / 64, M = lfa_ ? deg : 0;
+      for (size_t r = 0; r < risk.size(); ++r, ++x, lw += W, lm += M) {
+        const uint32_t ob = riskBefore.best[x], nb = after.best[x];
+        if (riskBefore.metric[x] == 0xFFFFFFFFu || after.metric[x] == 0xFFFFFFFFu || ob == nb) {
+          continue;
+        }
+        const auto& news = scan.anns[item[risk[r]]];
+        const auto* oe = entryOf(riskOld[r], ob);
+        const auto* ne = entryOf(news, nb);
+        const auto* neOld = entryOf(riskOld[r], nb); // (the new best, if it was an announcer: dirty?)
+        if (!oe || !ne || !(*oe == *ne) || (neOld && !(*neOld == *ne))) {
+          continue;
+        }
+        if ((!lfa_ && riskBefore.metric[x] != after.metric[x]) ||
+            !std::equal(after.links.begin() + lw, after.links.begin() + lw + W,
+                        riskBefore.links.begin() + lw) ||
+            !std::equal(after.lmet.begin() + lm, after.lmet.begin() + lm + M,
+                        riskBefore.lmet.begin() + lm)) {
+          continue;
+        }
+        suppress_[i].push_back(cols[risk[r]]); // only `best` moved, onto an equal entry
+      }
+      std::sort(suppress_[i].begin(), suppress_[i].end());
+      counts[i] -= (uint32_t)suppress_[i].size();
+    }
+  }
+  // the host's view of the columns
+  for (size_t k = 0; k < cols.size(); ++k) {
+    const uint32_t c = cols[k];
+    const size_t i = item[k];
+    const bool now = scan.keep[i] != 0;
+    if (!now && !isFree(c)) {
+      freeList_.push_back(c);
+    }
+    free_[slotOf(c)] = now ? 0 : 1;
+    // (a freed column keeps its prefix: this call's delta names it in the delete)
+    if (c < prefixes_.size()) {
+      if (now) {
+        prefixes_[c] = *scan.items[i].first;
+      }
+      announcers_[c] = std::move(scan.anns[i]);
+    } else {
+      if (now) {
+        sparePrefix_[c - spareBase()] = *scan.items[i].first;
+      }
+      spareAnn_[c - spareBase()] = std::move(scan.anns[i]);
+    }
+  }
+  rebuildServed();
+  diffed_ = true;
+  mapped_ = false;
+  patchDelta_ = true;
+  older_ = nullptr;
+  goneCols_.clear();
+  goneNew_.clear();
+  rowOf_.resize(names_.size());
+  for (uint32_t i = 0; i < rowOf_.size(); ++i) {
+    rowOf_[i] = i;
+  }
+  Counters::add("decision.route_table_patch_us", usSince(tp));
+  return counts;
 }
 
 std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string& node) const {
@@ -994,7 +1270,7 @@ std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string
     throw std::logic_error("AllNodesRouteTable::changedSplit: no diff has run");
   }
   auto it = ids_.find(node);
-  const size_t P = prefixes_.size(), C = P + owners_.size();
+  const size_t C = numCols();
   if (it == ids_.end() || (!C && goneCols_.empty())) {
     return {0, 0};
   }
@@ -1005,7 +1281,10 @@ std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string
     }
   }
   uint32_t uni = 0, lab = 0;
-  forEachSetBit(bits.data(), bits.size(), [&](size_t p) { (p < P ? uni : lab) += 1; });
+  forEachSetBit(bits.data(), bits.size(), [&](size_t p) { (isUni(p) ? uni : lab) += 1; });
+  if (patchDelta_) {
+    uni -= (uint32_t)suppress_[it->second].size();
+  }
   if (!goneCols_.empty()) {
     // deleted columns of the older table
     std::vector<uint64_t> gbits((goneCols_.size() + 63) / 64);
@@ -1018,7 +1297,7 @@ std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string
       if (p != SPF_MAP_NONE && ((bits[p / 64] >> (p % 64)) & 1)) {
         return; // the column changed its kind: counted as the update already
       }
-      (goneCols_[g] < older_->prefixes_.size() ? uni : lab) += 1;
+      (older_->isUni(goneCols_[g]) ? uni : lab) += 1;
     });
   }
   return {uni, lab};
@@ -1026,6 +1305,9 @@ std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string
 
 std::vector<int32_t> AllNodesRouteTable::labelCandidates(
     uint32_t i, const uint32_t* cols, size_t n, const uint32_t* gone, size_t ng) const {
+  if (patchDelta_) {
+    return {}; // a prefix change moves no label column and no adjacency label
+  }
   const uint32_t ia = rowOf_[i];
   const bool hasOld = ia != SPF_MAP_NONE;
   const size_t P = prefixes_.size(), Pa = older_->prefixes_.size();
@@ -1049,12 +1331,12 @@ std::vector<int32_t> AllNodesRouteTable::labelCandidates(
   }
   for (size_t k = 0; k < ng; ++k) {
     const uint32_t c = goneCols_[gone[k]];
-    if (c >= Pa) {
+    if (!older_->isUni(c)) {
       labels.insert(older_->owners_[c - Pa].label);
     }
   }
   for (size_t k = 0; k < n; ++k) {
-    if (cols[k] >= P) {
+    if (!isUni(cols[k])) {
       labels.insert(owners_[cols[k] - P].label);
     }
   }
@@ -1064,22 +1346,22 @@ std::vector<int32_t> AllNodesRouteTable::labelCandidates(
 void AllNodesRouteTable::unicastDelta(
     uint32_t i, const Row& r, const uint32_t* cols, size_t n, const uint32_t* gone, size_t ng,
     DecisionRouteUpdate& u) const {
-  const size_t P = prefixes_.size(), Pa = older_->prefixes_.size();
+  // (ng == 0 after applyPrefixChanges, where older_ is null)
   for (size_t k = 0; k < ng; ++k) {
     const uint32_t c = goneCols_[gone[k]];
     // (a column that changed its kind and still has a route here: the update
     // below replaces the older route)
-    if (c < Pa && !std::binary_search(cols, cols + n, goneNew_[gone[k]])) {
-      u.unicastRoutesToDelete.push_back(older_->prefixes_[c]);
+    if (older_->isUni(c) && !std::binary_search(cols, cols + n, goneNew_[gone[k]])) {
+      u.unicastRoutesToDelete.push_back(older_->prefixAt(c));
     }
   }
   for (size_t k = 0; k < n; ++k) {
     const size_t p = cols[k];
-    if (p >= P) {
+    if (!isUni(p)) {
       continue; // a label column: among the MPLS candidates
     }
     if (r.metricOf(p) == 0xFFFFFFFFu) {
-      u.unicastRoutesToDelete.push_back(prefixes_[p]);
+      u.unicastRoutesToDelete.push_back(prefixAt(p));
     } else {
       u.unicastRoutesToUpdate.push_back(materialise(names_[i], i, r, p));
     }
@@ -1110,7 +1392,7 @@ DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
     return u;
   }
   const uint32_t i = it->second;
-  const size_t C = prefixes_.size() + owners_.size();
+  const size_t C = numCols();
   // the bitmaps first: changed columns and, after a mapped diff, the set
   // bits of the gone bitmap (deleted columns of the older table)
   std::vector<uint32_t> cols, gone;
@@ -1119,7 +1401,11 @@ DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
     if (int s = spf_route_table_changed(table_.get(), i, bits.data()); s != SPF_OK) {
       tableFailure("spf_route_table_changed", s);
     }
-    forEachSetBit(bits.data(), bits.size(), [&](size_t p) { cols.push_back((uint32_t)p); });
+    forEachSetBit(bits.data(), bits.size(), [&](size_t p) {
+      if (!suppressed(i, (uint32_t)p)) {
+        cols.push_back((uint32_t)p);
+      }
+    });
   }
   if (mapped_ && !goneCols_.empty()) {
     std::vector<uint64_t> gbits((goneCols_.size() + 63) / 64);
@@ -1136,7 +1422,7 @@ DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
   unicastDelta(i, r, cols.data(), cols.size(), gone.data(), gone.size(), u);
   if (!labels.empty()) {
     const uint32_t ia = rowOf_[i];
-    const size_t Ca = older_->prefixes_.size() + older_->owners_.size();
+    const size_t Ca = older_->numCols();
     const Row o = ia != SPF_MAP_NONE && Ca ? older_->fetchRow(ia) : Row{};
     mplsDelta(i, r, ia, o, labels, u);
   }
@@ -1150,17 +1436,17 @@ uint64_t AllNodesRouteTable::deltaFetchBytes(const std::string& node) const {
   }
   const uint32_t i = it->second;
   auto rowBytes = [](const AllNodesRouteTable& t, uint32_t r) {
-    const uint64_t C = t.prefixes_.size() + t.owners_.size();
+    const uint64_t C = t.numCols();
     const uint64_t deg = t.row_[r + 1] - t.row_[r];
     // (tables with selected columns: the row's igp and winners words too)
     return C * (8 + ((deg + 63) / 64) * 8 + (t.lfa_ ? deg * 4 : 0)) + (uint64_t)t.nsel_ * 8;
   };
-  const uint64_t C = prefixes_.size() + owners_.size();
+  const uint64_t C = numCols();
   uint64_t b = ((C + 63) / 64) * 8 + rowBytes(*this, i);
   if (mapped_ && !goneCols_.empty()) {
     b += ((goneCols_.size() + 63) / 64) * 8;
   }
-  if (rowOf_[i] != SPF_MAP_NONE) {
+  if (older_ && rowOf_[i] != SPF_MAP_NONE) {
     b += rowBytes(*older_, rowOf_[i]);
   }
   return b;
@@ -1275,7 +1561,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
     return c;
   };
   const Cells cn = gather(*this, colsN, false);
-  const Cells co = gather(*older_, colsO, true);
+  const Cells co = older_ ? gather(*older_, colsO, true) : Cells{}; // (null: no candidates)
   const auto t3 = Clock::now();
 
   // a sparse Row over cells [k0, k1) of one node in a cell list
@@ -1311,8 +1597,18 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
                links.data() + lwBase[i], lmet.data() + lmBase[i],
                nsel_ ? igp.data() + k0 : nullptr)
         : Row{};
-    unicastDelta(i, r, col.data() + k0, (size_t)(k1 - k0), gone.data() + goneOff[i],
-                 (size_t)(goneOff[i + 1] - goneOff[i]), u);
+    if (patchDelta_ && !suppress_[i].empty()) {
+      std::vector<uint32_t> keep;
+      for (uint64_t k = k0; k < k1; ++k) {
+        if (!suppressed(i, col[k])) {
+          keep.push_back(col[k]);
+        }
+      }
+      unicastDelta(i, r, keep.data(), keep.size(), nullptr, 0, u);
+    } else {
+      unicastDelta(i, r, col.data() + k0, (size_t)(k1 - k0), gone.data() + goneOff[i],
+                   (size_t)(goneOff[i + 1] - goneOff[i]), u);
+    }
     if (labelsOf[i].empty()) {
       return;
     }

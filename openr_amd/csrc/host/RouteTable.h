@@ -82,19 +82,23 @@ class AllNodesRouteTable {
   // distance row, skipping unreachable candidates -- no all-reachable
   // requirement, split graphs are served.  bestPrefixEntry is the cell's
   // best candidate's, bestNexthop its loopback with metric = the cell's igp.
+  // spareColumns: that many extra columns with empty announcer lists, after
+  // the node-label columns (every other column keeps its index), for
+  // applyPrefixChanges to give to prefixes announced later.  An empty column
+  // has no route in any row; with 0 the table is what it was.
   // Left to the host: more than 32 candidates, a candidate vector with a
   // foreign entity of priority 3500 (its order against the IGP entity is
   // std::sort's), entries in another area.
   AllNodesRouteTable(
       const LinkState& ls, const PrefixState& ps, bool enableV4 = true, bool computeLfa = false,
       const std::unordered_set<std::string>* borderNodes = nullptr, bool bgpColumns = false,
-      bool bgpDryRun = false, bool bgpUseIgpMetric = false);
+      bool bgpDryRun = false, bool bgpUseIgpMetric = false, size_t spareColumns = 0);
   ~AllNodesRouteTable();
   AllNodesRouteTable(const AllNodesRouteTable&) = delete;
   AllNodesRouteTable& operator=(const AllNodesRouteTable&) = delete;
 
   size_t numNodes() const { return names_.size(); }
-  size_t numPrefixes() const { return prefixes_.size(); }
+  size_t numPrefixes() const { return prefixes().size(); }
   // device time of the all-sources SPF (+ next hops) and of the route kernel
   float spfMs() const { return spfMs_; }
   float routeMs() const { return routeMs_; }
@@ -178,7 +182,36 @@ class AllNodesRouteTable {
   bool diffWasMapped() const { return mapped_; }
   const std::string& nodeName(uint32_t id) const { return names_.at(id); }
   // the unicast prefixes the kernel serves (routes() covers exactly these)
-  const std::vector<thrift::IpPrefix>& prefixes() const { return prefixes_; }
+  // (after applyPrefixChanges: without the free columns, with the spare ones in use)
+  const std::vector<thrift::IpPrefix>& prefixes() const { return holes_ ? served_ : prefixes_; }
+
+  // Prefix changes in place (PrefixState::updatePrefixDatabase's changed
+  // sets, several merged if wanted; `ps` is the state now).  The topology is
+  // this table's snapshot: the caller asserts no link or node changed since
+  // it was built.  Every changed prefix is rescanned by the constructor's
+  // rules (scanPrefix) and, all in ONE spf_route_table_patch_columns:
+  //   served before and now: its column gets the new announcers (announcers
+  //     on both sides whose PrefixEntry differs are the column's dirty list);
+  //   served before, not now (withdrawn, no longer IP / SP_ECMP): the column
+  //     gets an empty list and becomes free;
+  //   served now, not before: it takes a free column -- one freed by an
+  //     earlier call first, else a spare one.  Too few: std::length_error
+  //     before anything is touched (rebuild the table).
+  // Throws std::invalid_argument, before anything is touched, on a table built
+  // with bgpColumns or borderNodes (BGP columns in place and AllAreasRouteTable
+  // are not covered; without bgpColumns a BGP prefix is not served and takes
+  // no column).  Afterwards prefixes(), routes(), countRoutes() describe the
+  // new state and changedSplit / delta / deltas the delta of this call, from
+  // the new cells alone (no older table; the MPLS lists are empty: label
+  // columns do not move).  A cell whose best announcer alone moved, between
+  // announcers with equal PrefixEntries, is no route change and is left out.
+  // Returns the changed routes per node, id order.
+  std::vector<uint32_t> applyPrefixChanges(
+      const PrefixState& ps, const std::unordered_set<thrift::IpPrefix>& changed);
+  // columns applyPrefixChanges can still give away
+  size_t freeColumns() const { return freeList_.size(); }
+  // device time of the last applyPrefixChanges (bitmap clear + spf_route_patch_kernel)
+  float patchMs() const { return patchMs_; }
   // BGP prefixes among them (bgpColumns), selected columns included
   size_t numBgpPrefixes() const { return nbgp_; }
   size_t numSelectedColumns() const { return nsel_; }
@@ -275,7 +308,7 @@ class AllNodesRouteTable {
   // found (keep: 0 not served, 1 Open/R, 2 BGP selected on the host, 3 a
   // selected column).
   struct PrefixScan {
-    const LinkState& ls;
+    const LinkState* ls; // (null in applyPrefixChanges: read for bgpColumns only)
     const PrefixState& ps;
     const std::unordered_set<std::string>* borderNodes;
     bool bgpColumns, bgpUseIgpMetric;
@@ -299,7 +332,44 @@ class AllNodesRouteTable {
   size_t nbgp_{0}, nsel_{0};
   bool bgpColumns_{false}, bgpDryRun_{false}, bgpIgp_{false};
   // 0 Open/R, 1 BGP selected on the host, 2 a selected column
-  int columnKind(size_t p) const { return sel_[p] ? 2 : bgp_[p] ? 1 : 0; }
+  // (a spare column is an Open/R one)
+  int columnKind(size_t p) const {
+    return p >= prefixes_.size() ? 0 : sel_[p] ? 2 : bgp_[p] ? 1 : 0;
+  }
+  // Column layout: [0, prefixes_.size()) the constructor's unicast columns,
+  // then owners_.size() node-label columns, then spare_ spare columns.  A
+  // unicast column has a slot: its index, or prefixes_.size() + j for spare
+  // column j.  free_[slot]: the column serves no prefix (its prefix entry is
+  // the last one it served, read by the delete of that call's delta).
+  size_t spare_{0};
+  std::vector<thrift::IpPrefix> sparePrefix_;
+  std::vector<std::vector<Announcer>> spareAnn_;
+  std::vector<uint8_t> free_;
+  std::vector<uint32_t> freeList_; // free columns, taken from the back
+  bool holes_{false};              // spare or freed columns exist: served_ is prefixes()
+  std::vector<thrift::IpPrefix> served_;
+  std::unordered_map<thrift::IpPrefix, uint32_t> colOfPrefix_; // served prefix -> column
+  bool hasBorder_{false};
+  bool patchDelta_{false}; // the last delta is applyPrefixChanges' (older_ is null)
+  float patchMs_{0};
+  // per node: columns of the last applyPrefixChanges whose cell changed in
+  // `best` alone, between announcers with equal PrefixEntries (no route change)
+  std::vector<std::vector<uint32_t>> suppress_;
+  bool suppressed(uint32_t i, uint32_t c) const {
+    return patchDelta_ && std::binary_search(suppress_[i].begin(), suppress_[i].end(), c);
+  }
+  size_t numCols() const { return prefixes_.size() + owners_.size() + spare_; }
+  size_t spareBase() const { return prefixes_.size() + owners_.size(); }
+  bool isUni(size_t c) const { return c < prefixes_.size() || c >= spareBase(); }
+  size_t slotOf(size_t c) const { return c < prefixes_.size() ? c : c - owners_.size(); }
+  bool isFree(size_t c) const { return !free_.empty() && free_[slotOf(c)]; }
+  const thrift::IpPrefix& prefixAt(size_t c) const {
+    return c < prefixes_.size() ? prefixes_[c] : sparePrefix_[c - spareBase()];
+  }
+  const std::vector<Announcer>& annsAt(size_t c) const {
+    return c < prefixes_.size() ? announcers_[c] : spareAnn_[c - spareBase()];
+  }
+  void rebuildServed();
   static bool sameSelection(const BgpSel& a, const BgpSel& b);
   // node-label columns: column prefixes_.size() + k is owners_[k]
   struct LabelOwner {

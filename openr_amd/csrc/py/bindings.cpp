@@ -478,14 +478,31 @@ PYBIND11_MODULE(_openr_spf, m) {
   py::class_<AllNodesRouteTable>(m, "AllNodesRouteTable")
       .def(py::init([](const AreaMapHolder& areas, const std::string& area, const PrefixState& ps,
                        bool enableV4, bool lfa, bool bgpColumns, bool bgpDryRun,
-                       bool bgpUseIgpMetric) {
+                       bool bgpUseIgpMetric, size_t spareColumns) {
              return std::make_unique<AllNodesRouteTable>(areas.map.at(area), ps, enableV4, lfa,
                                                          nullptr, bgpColumns, bgpDryRun,
-                                                         bgpUseIgpMetric);
+                                                         bgpUseIgpMetric, spareColumns);
            }),
            py::arg("areas"), py::arg("area"), py::arg("prefix_state"), py::arg("enable_v4") = true,
            py::arg("lfa") = false, py::arg("bgp_columns") = false, py::arg("bgp_dry_run") = false,
-           py::arg("bgp_use_igp_metric") = false, py::keep_alive<1, 2>())
+           py::arg("bgp_use_igp_metric") = false, py::arg("spare_columns") = 0,
+           py::keep_alive<1, 2>())
+      .def("apply_prefix_changes",
+           [](AllNodesRouteTable& t, const PrefixState& ps, const py::iterable& prefixes) {
+             // prefixes: the keys updatePrefixDatabase returns, (address bytes, length)
+             std::unordered_set<thrift::IpPrefix> changed;
+             for (const py::handle h : prefixes) {
+               const py::tuple k = py::reinterpret_borrow<py::tuple>(h);
+               thrift::IpPrefix p;
+               p.prefixAddress.addr = k[0].cast<std::string>();
+               p.prefixLength = k[1].cast<int16_t>();
+               changed.insert(std::move(p));
+             }
+             return t.applyPrefixChanges(ps, changed);
+           },
+           py::arg("prefix_state"), py::arg("prefixes"))
+      .def_property_readonly("free_columns", &AllNodesRouteTable::freeColumns)
+      .def_property_readonly("patch_ms", &AllNodesRouteTable::patchMs)
       .def_property_readonly("num_nodes", &AllNodesRouteTable::numNodes)
       .def_property_readonly("num_prefixes", &AllNodesRouteTable::numPrefixes)
       .def_property_readonly("num_bgp_prefixes", &AllNodesRouteTable::numBgpPrefixes)

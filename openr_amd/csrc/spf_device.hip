@@ -6490,6 +6490,309 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
   }
 }
 
+// The cell (q, p) of spf_route_table_kernel<false> for spf_route_patch_kernel:
+// s, d, nhq, W, NB, e0, deg, WL are the row's values as that kernel derives
+// them, `staged` says that st_* hold the row's links (rt_stage_row), and the
+// cell goes where `where` says: *metric_o, *best_o, lkp[WL] and (LFA, else
+// null) lm[deg].  A COPY of that kernel's loop body without its SEL branches,
+// not shared with it: called from there, even force-inlined and with the
+// output pointers derived at the same point, it cost both instances a VGPR
+// and SGPR spills.  A change of the cell goes into both.
+template <class Where>
+__device__ __forceinline__ void rt_cell(
+    const RouteTableArgs& a, uint32_t q, uint32_t p, uint32_t s, const uint32_t* d,
+    const uint8_t* nhq, uint32_t W, uint32_t NB, uint32_t e0, uint32_t deg, uint32_t WL,
+    bool staged, const uint32_t* st_nbr, const uint32_t* st_w, const uint32_t* st_slot,
+    const uint32_t* st_slotall, const uint32_t* st_dns, Where&& where) {
+  const uint32_t lo = a.ann_off[p], hi = a.ann_off[p + 1];
+  bool self = false;
+  uint32_t best = kInf32, reach = 0, undrained = 0;
+  for (uint32_t i = lo; i < hi; ++i) {
+    const uint32_t x = a.ann[i];
+    self |= x == s;
+    if (d[x] == kInf32) {
+      continue;
+    }
+    best = min(best, x);
+    ++reach;
+    undrained += (a.trbits[x >> 5] >> (x & 31)) & 1u;
+  }
+  uint32_t *metric_o, *best_o, *lm;
+  uint64_t* lkp;
+  where(metric_o, best_o, lkp, lm);
+  if (self || reach == 0) {
+    *metric_o = kInf32;
+    *best_o = kInf32;
+    for (uint32_t k = 0; k < WL; ++k) {
+      lkp[k] = 0;
+    }
+    for (uint32_t j = 0; lm && j < deg; ++j) {
+      lm[j] = kInf32;
+    }
+    return;
+  }
+  const bool filt = undrained > 0;
+  uint32_t mn = kInf32;
+  for (uint32_t i = lo; i < hi; ++i) {
+    const uint32_t x = a.ann[i];
+    if (d[x] != kInf32 && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+      mn = min(mn, d[x]);
+    }
+  }
+  *metric_o = mn;
+  *best_o = best;
+  if (staged && W <= kRtMaskWords) {
+    // OR of the next-hop masks of the min-cost announcers (registers),
+    // then slot -> link bits through the staged row (LDS broadcast)
+    uint64_t m[kRtMaskWords];
+#pragma unroll
+    for (uint32_t k = 0; k < kRtMaskWords; ++k) {
+      m[k] = 0;
+    }
+    for (uint32_t i = lo; i < hi; ++i) {
+      const uint32_t x = a.ann[i];
+      if (d[x] == mn && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+#pragma unroll
+        for (uint32_t k = 0; k < kRtMaskWords; ++k) {
+          if (k < W) {
+            m[k] |= nh_load(nhq, NB, W, x, k);
+          }
+        }
+      }
+    }
+    if (a.lfa) {
+      // getNextHopsWithMetric with LFA (Decision.cpp:1126-1175) and
+      // getNextHopsThrift without the shortest-metric filter: every up
+      // link to a next-hop node n, metric w(link) + value(n), value =
+      // mn - d(s, n) for shortest-path next hops, lowered to d(n, x) for
+      // any destination x with d(n, x) < mn + d(n, s) (RFC 5286)
+      for (uint32_t k = 0; k < WL; ++k) {
+        uint64_t out = 0;
+        const uint32_t j1 = min(deg, 64 * k + 64);
+        for (uint32_t j = 64 * k; j < j1; ++j) {
+          const uint32_t n = st_nbr[j], sl = st_slotall[j];
+          uint64_t w = 0;
+#pragma unroll
+          for (uint32_t kk = 0; kk < kRtMaskWords; ++kk) {
+            w = (sl >> 6) == kk ? m[kk] : w;
+          }
+          uint32_t v = ((w >> (sl & 63)) & 1ull) ? mn - d[n] : kInf32;
+          const uint32_t* rn = a.dist + (size_t)a.row_of[n] * a.Vp;
+          const uint64_t lim = (uint64_t)mn + st_dns[j];
+          for (uint32_t i = lo; i < hi; ++i) {
+            const uint32_t x = a.ann[i];
+            if (d[x] == kInf32 || (filt && !((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+              continue;
+            }
+            const uint32_t dx = rn[x];
+            if (dx != kInf32 && (uint64_t)dx < lim) {
+              v = min(v, dx);
+            }
+          }
+          lm[j] = v == kInf32 ? kInf32 : st_w[j] + v;
+          out |= (uint64_t)(v != kInf32) << (j & 63);
+        }
+        lkp[k] = out;
+      }
+      return;
+    }
+    for (uint32_t k = 0; k < WL; ++k) {
+      uint64_t out = 0;
+      const uint32_t j1 = min(deg, 64 * k + 64);
+      for (uint32_t j = 64 * k; j < j1; ++j) {
+        const uint32_t sl = st_slot[j];
+        uint64_t w = 0;
+#pragma unroll
+        for (uint32_t kk = 0; kk < kRtMaskWords; ++kk) {
+          w = (sl >> 6) == kk ? m[kk] : w;
+        }
+        out |= (sl == kInf32 ? 0ull : (w >> (sl & 63)) & 1ull) << (j & 63);
+      }
+      lkp[k] = out;
+    }
+    return;
+  }
+  // general path (high-degree source): word by word from HBM
+  for (uint32_t k = 0; k < WL; ++k) {
+    uint64_t out = 0;
+    const uint32_t j1 = min(deg, 64 * k + 64);
+    for (uint32_t j = 64 * k; j < j1; ++j) {
+      uint32_t sl;
+      if (staged) {
+        sl = st_slot[j];
+      } else {
+        const uint32_t nb = a.col[e0 + j];
+        sl = a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
+      }
+      if (sl == kInf32) {
+        continue;
+      }
+      uint64_t mm = 0;
+      for (uint32_t i = lo; i < hi && !mm; ++i) {
+        const uint32_t x = a.ann[i];
+        if (d[x] == mn && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+          mm = (nh_load(nhq, NB, W, x, sl >> 6) >> (sl & 63)) & 1ull;
+        }
+      }
+      out |= mm << (j & 63);
+    }
+    lkp[k] = out;
+  }
+}
+
+// the out-edges of row q's source into LDS, by `lanes` lanes of which this is
+// lane `lane` (the caller's barrier follows)
+__device__ __forceinline__ void rt_stage_row(
+    const RouteTableArgs& a, uint32_t s, const uint32_t* d, uint32_t e0, uint32_t deg,
+    uint32_t lane, uint32_t lanes, uint32_t* st_nbr, uint32_t* st_w, uint32_t* st_slot,
+    uint32_t* st_slotall, uint32_t* st_dns) {
+  for (uint32_t j = lane; j < deg; j += lanes) {
+    const uint32_t nb = a.col[e0 + j];
+    // a link is a shortest-path link iff metric(l) == d(s, nbr): keep
+    // the slot only for those (others can never be selected)
+    st_nbr[j] = nb;
+    st_w[j] = a.wout[e0 + j];
+    st_slot[j] = a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
+    if (a.lfa) {
+      st_slotall[j] = a.slot[e0 + j];
+      st_dns[j] = a.dist[(size_t)a.row_of[nb] * a.Vp + s];
+    }
+  }
+}
+
+// In-place patch of listed columns (spf_route_table_patch_columns): for row
+// rows[r] and listed column cols[kk], rt_cell computes the cell from the
+// resident SPF rows and the (already replaced) announcer lists into a scratch
+// cell, which is compared with the resident cell by the rule of the mapped
+// diff with identity maps (one side without a route; or metric -- not with
+// routes_only --, best, a link word or an LFA link metric differs; or the new
+// best is in the column's dirty list) and copied over it word by word where
+// the words differ.  The cell's bit is ORed into the (cleared) bitmap: listed
+// columns may share a word.  count[q] gets the row's changed cells.
+//
+// Launch shape: with a few columns per row the staging of the source's links
+// is the cost, not the cells, so RPW = 4 gives each wave of the workgroup a
+// row of its own and a quarter of the LDS stage (kRtStage / 4 links); its 64
+// lanes stride over the listed columns.  RPW = 1 is the full kernel's shape
+// (256 lanes over the columns, kRtStage links staged) for rows with more
+// links than a wave's slice holds and for long column lists.  Only LFA cells
+// NEED such a row staged (their code is on the staged path alone); a non-LFA
+// row of 257 .. 1,024 links would be correct unstaged in a wave, word by word
+// from HBM, and goes the same way so that it is staged too.  No grid stride: a workgroup takes RPW list entries, so its
+// one barrier is met by every wave, a wave without a row included.
+struct RoutePatchArgs {
+  RouteTableArgs t;          // the table's own arrays; metric_out .. lmet_out are the resident cells
+  const uint32_t* rows;      // [nrows] query rows
+  const uint32_t* cols;      // [k] listed columns
+  const uint32_t* dirty_off; // [k + 1] or null
+  const uint32_t* dirty_ann;
+  uint64_t* s_links;         // scratch cells: link words [lk_off[nq] / P * k]
+  uint32_t* s_lmet;          // [lm_off[nq] / P * k] (LFA)
+  uint64_t* bits;            // [nq * pw], cleared
+  uint32_t* count;           // [nq], zeroed
+  uint32_t nrows, k, pw, routes_only;
+};
+
+template <uint32_t RPW>
+__global__ __launch_bounds__(256) void spf_route_patch_kernel(RoutePatchArgs pa) {
+  constexpr uint32_t kStage = kRtStage / RPW, kLanes = 256 / RPW;
+  __shared__ uint32_t st_nbr[kRtStage];
+  __shared__ uint32_t st_w[kRtStage];
+  __shared__ uint32_t st_slot[kRtStage];
+  __shared__ uint32_t st_slotall[kRtStage];
+  __shared__ uint32_t st_dns[kRtStage];
+  const RouteTableArgs& a = pa.t;
+  const uint32_t sub = threadIdx.x / kLanes, lane = threadIdx.x % kLanes;
+  const uint32_t ri = blockIdx.x * RPW + sub;
+  const bool live = ri < pa.nrows; // uniform over the row's waves
+  const uint32_t q = live ? pa.rows[ri] : 0;
+  const uint32_t s = a.src[q];
+  const uint32_t* d = a.dist + (size_t)q * a.Vp;
+  const uint32_t e0 = a.row[s], deg = a.row[s + 1] - e0;
+  const bool staged = deg <= kStage;
+  uint32_t* nbr = st_nbr + sub * kStage;
+  uint32_t* w = st_w + sub * kStage;
+  uint32_t* slot = st_slot + sub * kStage;
+  uint32_t* slotall = st_slotall + sub * kStage;
+  uint32_t* dns = st_dns + sub * kStage;
+  if (live && staged) {
+    rt_stage_row(a, s, d, e0, deg, lane, kLanes, nbr, w, slot, slotall, dns);
+  }
+  __syncthreads();
+  if (!live) {
+    return;
+  }
+  const uint8_t* nhq = a.nh + a.nh_off[q];
+  const uint32_t W = a.nh_w[q], NB = a.nh_b[q];
+  const uint32_t WL = (deg + 63) / 64;
+  // the row's scratch cells: k of them where the table has P
+  uint64_t* slk = pa.s_links + a.lk_off[q] / a.P * pa.k;
+  uint32_t* slm = a.lfa ? pa.s_lmet + a.lm_off[q] / a.P * pa.k : nullptr;
+  uint64_t* lk = a.link_out + a.lk_off[q];
+  uint32_t n = 0;
+  for (uint32_t kk = lane; kk < pa.k; kk += kLanes) {
+    const uint32_t p = pa.cols[kk];
+    uint32_t nm, nbest;
+    uint64_t* nl = slk + (size_t)kk * WL;
+    uint32_t* nlm = slm ? slm + (size_t)kk * deg : nullptr;
+    rt_cell(a, q, p, s, d, nhq, W, NB, e0, deg, WL, staged, nbr, w, slot, slotall, dns,
+                   [&](uint32_t*& metric_o, uint32_t*& best_o, uint64_t*& lkp, uint32_t*& lm) {
+                     metric_o = &nm;
+                     best_o = &nbest;
+                     lkp = nl;
+                     lm = nlm;
+                   });
+    const size_t o = (size_t)q * a.P + p;
+    uint64_t* ol = lk + (size_t)p * WL;
+    uint32_t* olm = slm ? a.lmet_out + a.lm_off[q] + (size_t)p * deg : nullptr;
+    const uint32_t om = a.metric_out[o], ob = a.best_out[o];
+    bool ch;
+    if (om == kInf32 || nm == kInf32) {
+      ch = om != nm;
+    } else {
+      bool dirty = false;
+      if (pa.dirty_off) {
+        for (uint32_t i = pa.dirty_off[kk], e = pa.dirty_off[kk + 1]; i < e; ++i) {
+          dirty |= pa.dirty_ann[i] == nbest;
+        }
+      }
+      ch = (om != nm && !pa.routes_only) || ob != nbest || dirty;
+    }
+    if (om != nm) {
+      a.metric_out[o] = nm;
+    }
+    if (ob != nbest) {
+      a.best_out[o] = nbest;
+    }
+    // (a cell without a route has clear link words and kInf32 link metrics:
+    // with one side routeless the words below differ only where ch is set)
+    for (uint32_t k = 0; k < WL; ++k) {
+      const uint64_t x = nl[k];
+      if (ol[k] != x) {
+        ol[k] = x;
+        ch = true;
+      }
+    }
+    for (uint32_t j = 0; olm && j < deg; ++j) {
+      const uint32_t x = nlm[j];
+      if (olm[j] != x) {
+        olm[j] = x;
+        ch = true;
+      }
+    }
+    if (ch) {
+      atomicOr((unsigned long long*)&pa.bits[(size_t)q * pa.pw + (p >> 6)], 1ull << (p & 63));
+      ++n;
+    }
+  }
+  for (uint32_t off = 32; off; off >>= 1) {
+    n += __shfl_down(n, off);
+  }
+  if ((threadIdx.x & 63u) == 0 && n) {
+    atomicAdd(&pa.count[q], n);
+  }
+}
+
 // BGP best path per node with the IGP cost in the metric vector
 // (spf_route_table_create_sel; SpfSolverImpl::runBestPathSelectionBgp,
 // Decision.cpp:714-803, with bgpUseIgpMetric :746-766, then selectEcmpBgp
@@ -14693,6 +14996,18 @@ struct spf_route_table {
   DevBuf<uint16_t> d_pair;
   DevBuf<uint8_t> d_cflags;
   DevEvent evs0;
+  // spf_route_table_patch_columns: host copies of the announcer arrays (and
+  // the candidate flags laid out like them), from which the patched arrays
+  // are assembled; the rows by launch shape (those with at most kRtStage / 4
+  // links first: pt_wave of them); the call's lists and scratch cells
+  // (grow-only); evp0 .. evp1 time the patch kernel
+  std::vector<uint32_t> h_ann_off, h_ann;
+  std::vector<uint8_t> h_cflags;
+  DevBuf<uint32_t> d_pt_rows, d_pt_cols, d_pt_doff, d_pt_dann, d_pt_lmet;
+  DevBuf<uint64_t> d_pt_links;
+  uint32_t pt_wave = 0;
+  DevEvent evp0, evp1;
+  bool patched = false;
 };
 
 namespace {
@@ -14825,6 +15140,8 @@ int spf_route_table_create_ex(
   if (t->ev0.create() != hipSuccess || t->ev1.create() != hipSuccess) {
     return bail(fail(SPF_E_DEVICE, "hipEventCreate"));
   }
+  t->h_ann.assign(announcers, announcers + na);
+  t->h_ann_off = std::move(off);
   *out = t;
   return SPF_OK;
 }
@@ -14884,6 +15201,7 @@ int spf_route_table_create_sel(
   t->sel_col.assign(sel->columns, sel->columns + S);
   t->sel_of = sel_of;
   const uint32_t na = ann_offsets[num_prefixes];
+  t->h_cflags.assign(sel->cand_flags, sel->cand_flags + na);
   const size_t cells = (size_t)q->nq * S;
   int st = SPF_OK;
   if ((st = t->d_sel_col.upload(sel->columns, (size_t)S)) ||
@@ -15457,6 +15775,245 @@ int spf_route_table_changed_gone(spf_route_table* t, uint32_t i, uint64_t* bits)
   HIP_TRY(hipSetDevice(t->q->g->device));
   HIP_TRY(hipStreamSynchronize(t->q->g->stream));
   HIP_TRY(hipMemcpy(bits, t->d_gone + (size_t)i * gw, (size_t)gw * 8, hipMemcpyDeviceToHost));
+  return SPF_OK;
+}
+
+int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
+                                  uint32_t* changed) {
+  SPF_ABI_RANGE("spf_route_table_patch_columns");
+  if (!t || !p) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  if (!t->ran) {
+    return fail(SPF_E_INVALID, "table has not run");
+  }
+  spf_query* q = t->q;
+  spf_graph* g = q->g;
+  const uint32_t k = p->num_columns, P = t->P, nq = q->nq, pw = (P + 63) / 64;
+  // every check before anything is modified
+  uint32_t na = 0, nd = 0;
+  if (k) {
+    if (!p->columns || !p->ann_offsets) {
+      return fail(SPF_E_INVALID, "null columns / ann_offsets");
+    }
+    if (p->ann_offsets[0] != 0 || (p->dirty_off && p->dirty_off[0] != 0)) {
+      return fail(SPF_E_INVALID, "offsets do not start at 0");
+    }
+    if (int st = check_ann_offsets_monotone(p->ann_offsets, k); st != SPF_OK) {
+      return st;
+    }
+    if (p->dirty_off) {
+      if (int st = check_ann_offsets_monotone(p->dirty_off, k); st != SPF_OK) {
+        return st;
+      }
+      nd = p->dirty_off[k];
+    }
+    na = p->ann_offsets[k];
+    if ((na && !p->announcers) || (nd && !p->dirty_ann)) {
+      return fail(SPF_E_INVALID, "null announcers / dirty_ann");
+    }
+    for (uint32_t i = 0; i < na; ++i) {
+      if (p->announcers[i] >= g->V) {
+        return fail(SPF_E_INVALID, "announcer out of range");
+      }
+    }
+    for (uint32_t i = 0; i < nd; ++i) {
+      if (p->dirty_ann[i] >= g->V) { // SPF_MAP_NONE included: best is part of every patched cell
+        return fail(SPF_E_INVALID, "dirty announcer out of range");
+      }
+    }
+    std::vector<uint8_t> seen(P, 0);
+    for (uint32_t i = 0; i < k; ++i) {
+      const uint32_t c = p->columns[i];
+      if (c >= P || seen[c]) {
+        return fail(SPF_E_INVALID, "column out of range or listed twice");
+      }
+      seen[c] = 1;
+    }
+    for (uint32_t i = 0; i < k; ++i) {
+      if (is_selected(t, p->columns[i])) {
+        return fail(SPF_E_UNSUPPORTED, "a selected column cannot be patched (its pair tables "
+                                       "would have to be replaced: rebuild the table)");
+      }
+    }
+  }
+  HIP_TRY(hipSetDevice(g->device));
+  // the patched announcer arrays, assembled beside the resident ones
+  std::vector<uint32_t> off, ann;
+  std::vector<uint8_t> cflags;
+  DevBuf<uint32_t> d_off, d_ann;
+  DevBuf<uint8_t> d_cflags;
+  if (k) {
+    std::vector<uint32_t> at(P, kInf32); // column -> index into the patch
+    for (uint32_t i = 0; i < k; ++i) {
+      at[p->columns[i]] = i;
+    }
+    off.assign((size_t)P + 1, 0);
+    ann.reserve(t->h_ann.size() + na);
+    for (uint32_t c = 0; c < P; ++c) {
+      const uint32_t i = at[c];
+      const uint32_t* src = i != kInf32 ? p->announcers + p->ann_offsets[i]
+                                        : t->h_ann.data() + t->h_ann_off[c];
+      const uint32_t n = i != kInf32 ? p->ann_offsets[i + 1] - p->ann_offsets[i]
+                                     : t->h_ann_off[c + 1] - t->h_ann_off[c];
+      if ((uint64_t)ann.size() + n > 0xFFFFFFFFull) {
+        return fail(SPF_E_INVALID, "more than 2^32 announcers");
+      }
+      if (t->S) { // candidate flags keep the announcers' layout (read in selected columns only)
+        const size_t at0 = cflags.size();
+        cflags.resize(at0 + n, 0);
+        if (i == kInf32 && n) {
+          std::copy_n(t->h_cflags.begin() + t->h_ann_off[c], n, cflags.begin() + at0);
+        }
+      }
+      if (n) {
+        ann.insert(ann.end(), src, src + n);
+      }
+      off[c + 1] = (uint32_t)ann.size();
+    }
+    int st = SPF_OK;
+    if ((st = d_off.upload(off.data(), off.size())) || (st = d_ann.upload(ann.data(), ann.size())) ||
+        (st = d_cflags.upload(cflags.data(), cflags.size()))) {
+      return st;
+    }
+    if (nq) {
+      if ((st = t->d_pt_cols.upload(p->columns, k)) ||
+          (st = t->d_pt_doff.upload(p->dirty_off, p->dirty_off ? (size_t)k + 1 : 0)) ||
+          (st = t->d_pt_dann.upload(p->dirty_ann, nd))) {
+        return st;
+      }
+      if (t->d_pt_links.reserve((size_t)(t->lk_off.back() / P * k)) != hipSuccess ||
+          t->d_pt_lmet.reserve((size_t)(t->lm_off.back() / P * k)) != hipSuccess) {
+        return fail(SPF_E_NOMEM, "route patch scratch cells");
+      }
+      if (!t->d_pt_rows) {
+        // rows by launch shape: a wave's LDS slice holds kRtStage / 4 links
+        std::vector<uint32_t> rows;
+        rows.reserve(nq);
+        for (uint32_t i = 0; i < nq; ++i) {
+          if (t->deg[i] <= kRtStage / 4) {
+            rows.push_back(i);
+          }
+        }
+        const uint32_t nw = (uint32_t)rows.size();
+        for (uint32_t i = 0; i < nq; ++i) {
+          if (t->deg[i] > kRtStage / 4) {
+            rows.push_back(i);
+          }
+        }
+        if ((st = t->d_pt_rows.upload(rows.data(), rows.size()))) {
+          return st;
+        }
+        t->pt_wave = nw;
+      }
+    }
+  }
+  if (nq) {
+    HIP_TRY(t->d_count.reserve(nq));
+    HIP_TRY(t->d_diff.reserve((size_t)nq * pw)); // (the size every diff of this table asks for)
+    if (!t->evp0.e && (t->evp0.create() != hipSuccess || t->evp1.create() != hipSuccess)) {
+      return fail(SPF_E_DEVICE, "hipEventCreate");
+    }
+  }
+  // accepted.  Earlier work on the stream (spf_route_table_run is
+  // asynchronous) may still read the resident announcer arrays: it ends
+  // before they are released
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  if (k) {
+    t->d_ann_off = std::move(d_off); // (the old arrays go with d_off / d_ann / d_cflags)
+    t->d_ann = std::move(d_ann);
+    t->h_ann_off = std::move(off);
+    t->h_ann = std::move(ann);
+    if (t->S) {
+      t->d_cflags = std::move(d_cflags);
+      t->h_cflags = std::move(cflags);
+    }
+  }
+  ++t->epoch;
+  t->diffed = true;
+  t->diff_mapped_last = false;
+  t->mapped = true; // spf_route_table_changed_gone: no gone columns
+  t->gone_n = 0;
+  t->patched = true;
+  if (nq == 0) {
+    return SPF_OK;
+  }
+  HIP_TRY(hipMemsetAsync(t->d_count, 0, (size_t)nq * 4, g->stream));
+  if (pw) {
+    HIP_TRY(hipMemsetAsync(t->d_diff, 0, (size_t)nq * pw * 8, g->stream));
+  }
+  HIP_TRY(hipEventRecord(t->evp0, g->stream));
+  if (k) {
+    RoutePatchArgs a{};
+    a.t.row = g->d_row;
+    a.t.col = g->d_col;
+    a.t.wout = g->d_wout;
+    a.t.slot = g->d_slot;
+    a.t.trbits = g->d_tr;
+    a.t.src = q->d_src;
+    a.t.dist = (const uint32_t*)q->d_dist;
+    a.t.nh = q->d_nhb;
+    a.t.nh_off = q->d_nhb_off;
+    a.t.nh_b = q->d_nh_b;
+    a.t.nh_w = q->d_nh_w;
+    a.t.ann_off = t->d_ann_off;
+    a.t.ann = t->d_ann;
+    a.t.lk_off = t->d_lk_off;
+    a.t.metric_out = t->d_metric;
+    a.t.best_out = t->d_best;
+    a.t.link_out = t->d_links;
+    a.t.row_of = t->d_row_of;
+    a.t.lm_off = t->d_lm_off;
+    a.t.lmet_out = t->d_lmet;
+    a.t.lfa = t->lfa ? 1u : 0u;
+    a.t.Vp = q->Vp;
+    a.t.P = P;
+    a.t.nq = nq;
+    a.cols = t->d_pt_cols;
+    a.dirty_off = p->dirty_off ? t->d_pt_doff.p : nullptr;
+    a.dirty_ann = t->d_pt_dann;
+    a.s_links = t->d_pt_links;
+    a.s_lmet = t->d_pt_lmet;
+    a.bits = t->d_diff;
+    a.count = t->d_count;
+    a.k = k;
+    a.pw = pw;
+    a.routes_only = t->diff_routes ? 1u : 0u;
+    // long lists: 256 lanes per row; else a wave per row where its LDS slice holds the row's links
+    const uint32_t nwave = k > 256 ? 0 : t->pt_wave;
+    if (nwave) {
+      a.rows = t->d_pt_rows;
+      a.nrows = nwave;
+      SPF_LAUNCH_AS("spf_route_patch_kernel", spf_route_patch_kernel<4>, dim3((nwave + 3) / 4),
+                    dim3(256), 0, g->stream, a);
+      HIP_TRY(hipGetLastError());
+    }
+    if (nwave < nq) {
+      a.rows = t->d_pt_rows + nwave;
+      a.nrows = nq - nwave;
+      SPF_LAUNCH_AS("spf_route_patch_kernel", spf_route_patch_kernel<1>, dim3(nq - nwave),
+                    dim3(256), 0, g->stream, a);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  HIP_TRY(hipEventRecord(t->evp1, g->stream));
+  if (changed) {
+    HIP_TRY(hipMemcpyAsync(changed, t->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, g->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  return SPF_OK;
+}
+
+int spf_route_table_patch_elapsed_ms(spf_route_table* t, float* ms) {
+  if (!t || !ms || !t->patched) {
+    return fail(SPF_E_INVALID, "no patch to time");
+  }
+  *ms = 0.f;
+  if (!t->evp1.e) {
+    return SPF_OK;
+  }
+  HIP_TRY(hipEventSynchronize(t->evp1));
+  HIP_TRY(hipEventElapsedTime(ms, t->evp0, t->evp1));
   return SPF_OK;
 }
 
