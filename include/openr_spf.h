@@ -603,8 +603,50 @@ typedef struct spf_route_patch {
  * the patch.  The scratch cells it keeps are num_columns / P of the table's. */
 int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
                                   uint32_t* changed /*[rows] or NULL*/);
-/* Device time of the last spf_route_table_patch_columns (clearing the bitmap
- * and spf_route_patch_kernel). */
+/* spf_route_table_patch_columns for tables with selected columns (BGP
+ * columns): `p` means what it means there; `sel` describes the listed columns
+ * that are selected columns of `t`.  sel->columns holds table column indices,
+ * each also in p->columns and a selected column of `t`; every listed column
+ * that is selected in `t` must appear in it.  sel->pair_offsets / pair_codes
+ * are the NEW pair tables of those columns (at least n(n-1)/2 entries each,
+ * n <= 32 candidates), sel->cand_flags is parallel to p->announcers (entries of
+ * unselected columns are ignored).  A column's kind is fixed at creation: the
+ * [rows][S] selection words and the table's selected set do not move, so `sel`
+ * cannot turn an unselected column into a selected one or back.  A table gets
+ * spare selected columns by being created with selected columns whose
+ * candidate list is empty.
+ * In this call only, the dirty list of an UNSELECTED column may hold
+ * SPF_MAP_NONE, with the meaning of spf_route_diff_map::dirty_ann: best is
+ * not compared in that column (a BGP column selected once on the host).
+ * After the call every cell of `t` is bit-equal to the cell of a table freshly
+ * created over the same query with spf_route_table_create_sel, the patched
+ * announcer lists, pair tables and flags, and run: metric, best, link words,
+ * (SPF_RT_LFA) link metrics and what spf_route_table_fetch_sel reads, igp and
+ * winners.  The resident announcer, flag, pair-offset and pair arrays are
+ * replaced (later columns' offsets shift when a list changes its length): a
+ * later spf_route_table_run reproduces the patched cells.
+ * The changed bitmap equals what spf_route_table_diff_mapped(before, after,
+ * map) reports with identity maps and the given dirty lists, its rule for a
+ * column selected on both sides included: a cell with a route before and after
+ * whose igp word differs is set.  spf_route_table_diff_routes is honoured.
+ * `t` is left as after an equal-layout diff, as by the call above; in addition
+ * spf_route_table_delta_fetch_igp and _fetch_cells_igp return the new igp
+ * words.
+ * Everything is checked on the host first; on an error the table, its bitmap
+ * and its pack state are as before the call.  SPF_E_INVALID: everything the
+ * call above rejects (but a selected column, which is accepted here); a `sel`
+ * column that `p` does not list, that is not a selected column of `t` or that
+ * is listed twice; a listed selected column missing from `sel`; more than 32
+ * candidates; a pair table shorter than n(n-1)/2; pair_offsets[0] != 0 or
+ * decreasing offsets; a null array that is needed; SPF_MAP_NONE in the dirty
+ * list of a selected column.  With `sel` NULL or empty and no listed column
+ * selected the call behaves as the one above, apart from the SPF_MAP_NONE
+ * rule. */
+int spf_route_table_patch_columns_sel(
+    spf_route_table* t, const spf_route_patch* p, const spf_route_select_desc* sel,
+    uint32_t* changed /*[rows] or NULL*/);
+/* Device time of the last spf_route_table_patch_columns or _patch_columns_sel
+ * (clearing the bitmap and spf_route_patch_kernel). */
 int spf_route_table_patch_elapsed_ms(spf_route_table* t, float* ms);
 
 /* The delta itself (getRouteDelta, Decision.cpp:47-85: the updates and

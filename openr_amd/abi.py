@@ -103,6 +103,7 @@ EXPORTED_SYMBOLS = (
     "spf_route_table_fetch_cells_igp",
     "spf_route_table_diff_routes",
     "spf_route_table_patch_columns",
+    "spf_route_table_patch_columns_sel",
     "spf_route_table_patch_elapsed_ms",
     "spf_cluster_unique_id",
     "spf_cluster_create_local",
@@ -321,6 +322,32 @@ def _route_patch(columns, announcers, dirty=None):
     return _RoutePatch(k, *ptr), keep
 
 
+def _route_patch_sel(columns, announcers, selected):
+    """(spf_route_select_desc of a patch, arrays it points into): selected is
+    {column: (pair_codes, cand_flags)} for listed columns, cand_flags parallel
+    to the column's new announcers[k]."""
+    at = {int(c): k for k, c in enumerate(columns)}
+    off = np.zeros(len(columns) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(a) for a in announcers])
+    cols = np.asarray(sorted(selected), dtype=np.uint32)
+    poff = np.zeros(len(cols) + 1, dtype=np.uint64)
+    codes, cflags = [], np.zeros(max(int(off[-1]), 1), dtype=np.uint8)
+    for j, c in enumerate(cols):
+        pc, cf = selected[int(c)]
+        codes.extend(int(x) for x in pc)
+        poff[j + 1] = len(codes)
+        k = at.get(int(c))
+        if k is not None:  # (a column the patch does not list is the library's to refuse)
+            n = min(len(cf), len(announcers[k]))
+            cflags[off[k]:off[k] + n] = cf[:n]
+    pcs = np.asarray(codes if codes else [0], dtype=np.uint16)
+    cols_arr = cols if len(cols) else np.zeros(1, dtype=np.uint32)
+    keep = [cols_arr, poff, pcs, cflags]
+    d = _RouteSelectDesc(len(cols), _p(cols_arr, C.c_uint32), _p(poff, C.c_uint64),
+                         _p(pcs, C.c_uint16), _p(cflags, C.c_uint8))
+    return d, keep
+
+
 _lib = None
 
 
@@ -465,6 +492,8 @@ def load():
         "spf_route_table_delta_fetch_igp": (C.c_int, [vp, pu32]),
         "spf_route_table_diff_routes": (C.c_int, [vp, C.c_int]),
         "spf_route_table_patch_columns": (C.c_int, [vp, C.POINTER(_RoutePatch), pu32]),
+        "spf_route_table_patch_columns_sel": (C.c_int, [vp, C.POINTER(_RoutePatch),
+                                                        C.POINTER(_RouteSelectDesc), pu32]),
         "spf_route_table_patch_elapsed_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "spf_route_table_fetch_cells_igp": (C.c_int, [vp, C.c_uint64, pu32, pu32, pu32]),
     }
@@ -1183,8 +1212,24 @@ class RouteTable:
         del keep
         return out[: self.n]
 
+    def patch_columns_sel(self, columns, announcers, selected, dirty=None) -> np.ndarray:
+        """spf_route_table_patch_columns_sel: patch_columns for tables with
+        selected columns.  selected is {column: (pair_codes, cand_flags)} for
+        the listed columns that are selected ones, as the constructor takes it
+        (cand_flags parallel to the column's new announcer list).  A dirty list
+        of an unselected column may hold SPF_MAP_NONE (best is not compared)."""
+        m, keep = _route_patch(columns, announcers, dirty)
+        d, keep_sel = _route_patch_sel(columns, announcers, selected or {})
+        out = np.zeros(max(self.n, 1), dtype=np.uint32)
+        _check(load().spf_route_table_patch_columns_sel(self.h, C.byref(m), C.byref(d),
+                                                        _p(out, C.c_uint32)),
+               "spf_route_table_patch_columns_sel")
+        self.num_gone = 0
+        del keep, keep_sel
+        return out[: self.n]
+
     def patch_ms(self) -> float:
-        """Device time of the last patch_columns."""
+        """Device time of the last patch_columns / patch_columns_sel."""
         ms = C.c_float()
         _check(load().spf_route_table_patch_elapsed_ms(self.h, C.byref(ms)),
                "spf_route_table_patch_elapsed_ms")

@@ -185,7 +185,7 @@ void AllNodesRouteTable::scanPrefix(PrefixScan& s, size_t i) const {
     // maybeFilterDrainedNodes (Decision.cpp:651-666)
     std::set<std::string> undrained;
     for (const auto& w : winners) {
-      if (!s.ls->isNodeOverloaded(w)) {
+      if (!(s.ls ? s.ls->isNodeOverloaded(w) : overloaded_[ids_.at(w)] != 0)) {
         undrained.insert(w);
       }
     }
@@ -211,7 +211,7 @@ void AllNodesRouteTable::scanPrefix(PrefixScan& s, size_t i) const {
 // own row answers for every node
 void AllNodesRouteTable::dropUnreachableBgp(PrefixScan& s) const {
   const uint32_t V = (uint32_t)names_.size();
-  std::unordered_map<uint32_t, bool> reachesAll;
+  auto& reachesAll = reachesAll_; // (the rows are the snapshot's: an answer holds for the table's life)
   std::vector<uint32_t> rowBuf(V);
   for (size_t i = 0; i < s.items.size(); ++i) {
     if (s.keep[i] != 2) {
@@ -347,6 +347,15 @@ void AllNodesRouteTable::createAndRunTable(
     }
   }
   nsel_ = selColumns.size();
+  ctorSel_.assign(prefixes_.size(), 0);
+  for (const uint32_t p : selColumns) {
+    ctorSel_[p] = 1;
+  }
+  for (size_t j = 0; j < spareSel_; ++j) { // spare selected columns: no candidates, no pair codes
+    selColumns.push_back((uint32_t)(spareBase() + spare_ + j));
+    pairOff.push_back(pairCodes.size());
+  }
+  devSel_ = selColumns.size();
   spf_route_select_desc sd{};
   sd.num_selected = (uint32_t)selColumns.size();
   sd.columns = selColumns.data();
@@ -357,7 +366,7 @@ void AllNodesRouteTable::createAndRunTable(
   spf_route_table* table = nullptr;
   if ((s = spf_route_table_create_sel(
            query_.get(), (uint32_t)numCols(), annOff.data(),
-           ann.empty() ? nullptr : ann.data(), lfa_ ? SPF_RT_LFA : 0u, nsel_ ? &sd : nullptr,
+           ann.empty() ? nullptr : ann.data(), lfa_ ? SPF_RT_LFA : 0u, devSel_ ? &sd : nullptr,
            &table)) != SPF_OK) {
     tableFailure("spf_route_table_create", s);
   }
@@ -386,14 +395,16 @@ void AllNodesRouteTable::createAndRunTable(
 AllNodesRouteTable::AllNodesRouteTable(
     const LinkState& ls, const PrefixState& ps, bool enableV4, bool computeLfa,
     const std::unordered_set<std::string>* borderNodes, bool bgpColumns, bool bgpDryRun,
-    bool bgpUseIgpMetric, size_t spareColumns)
+    bool bgpUseIgpMetric, size_t spareColumns, bool bgpInPlace, size_t spareSelectedColumns)
     : area_(ls.getArea()),
       enableV4_(enableV4),
       lfa_(computeLfa),
       bgpColumns_(bgpColumns),
       bgpDryRun_(bgpDryRun),
       bgpIgp_(bgpUseIgpMetric),
+      bgpInPlace_(bgpInPlace),
       spare_(spareColumns),
+      spareSel_(bgpColumns && bgpUseIgpMetric ? spareSelectedColumns : 0),
       hasBorder_(borderNodes != nullptr) {
   auto tp = std::chrono::steady_clock::now();
   LinkState::Engine& eng = ls.engine();
@@ -405,6 +416,7 @@ AllNodesRouteTable::AllNodesRouteTable(
   }
   names_ = eng.names;
   ids_ = eng.ids;
+  overloaded_.assign(eng.overloaded.begin(), eng.overloaded.end());
   row_ = eng.row;
   halfLink_.resize(eng.col.size());
   for (size_t e = 0; e < eng.col.size(); ++e) {
@@ -480,15 +492,19 @@ AllNodesRouteTable::AllNodesRouteTable(
   Counters::add("decision.route_table_prefixes_us", usSince(tp));
   addNodeLabelColumns(ls, annOff, ann);
   Counters::add("decision.route_table_labels_us", usSince(tp));
-  if (spare_) {
-    // spare columns: empty lists after the label columns, all free
-    annOff.insert(annOff.end(), spare_, (uint32_t)ann.size());
-    sparePrefix_.resize(spare_);
-    spareAnn_.resize(spare_);
-    free_.assign(prefixes_.size() + spare_, 0);
-    for (size_t j = spare_; j-- > 0;) {
+  if (spare_ + spareSel_) {
+    // spare columns: empty lists after the label columns, all free; the spare
+    // selected columns after them
+    annOff.insert(annOff.end(), spare_ + spareSel_, (uint32_t)ann.size());
+    sparePrefix_.resize(spare_ + spareSel_);
+    spareAnn_.resize(spare_ + spareSel_);
+    bgp_.resize(prefixes_.size() + spare_ + spareSel_);
+    sel_.resize(prefixes_.size() + spare_ + spareSel_);
+    free_.assign(prefixes_.size() + spare_ + spareSel_, 0);
+    for (size_t j = spare_ + spareSel_; j-- > 0;) {
       free_[prefixes_.size() + j] = 1;
-      freeList_.push_back((uint32_t)(spareBase() + j)); // (taken from the back: ascending)
+      // (taken from the back: ascending)
+      (j < spare_ ? freeList_ : freeSelList_).push_back((uint32_t)(spareBase() + j));
     }
     rebuildServed();
   }
@@ -536,7 +552,7 @@ AllNodesRouteTable::Row AllNodesRouteTable::fetchRow(uint32_t i) const {
   r.metric.resize(P);
   r.best.resize(P);
   r.links.resize(std::max<size_t>(1, P * r.W));
-  if (nsel_) {
+  if (devSel_) {
     r.igp.resize(P);
     std::vector<uint32_t> winners(P);
     if (int s = spf_route_table_fetch_sel(table_.get(), i, r.metric.data(), r.best.data(),
@@ -582,21 +598,22 @@ RibUnicastEntry AllNodesRouteTable::materialise(
     // selectEcmpBgp (Decision.cpp:805-866) per node: the cell's best
     // candidate, its loopback with the cell's igp as metric
     // (PrefixState.cpp:111-126)
-    const SelCol& sc = *sel_[p];
-    for (size_t c = 0; c < announcers_[p].size(); ++c) {
-      if (announcers_[p][c].id == r.bestOf(p) && sc.via[c]) {
+    const SelCol& sc = selAt(p);
+    const auto& cands = annsAt(p);
+    for (size_t c = 0; c < cands.size(); ++c) {
+      if (cands[c].id == r.bestOf(p) && sc.via[c]) {
         thrift::NextHopThrift via = *sc.via[c];
         via.metric = (int32_t)r.igp[r.at(p)];
-        return RibUnicastEntry(prefixes_[p], std::move(nhs), announcers_[p][c].entry, area_,
-                               bgpDryRun_, via);
+        return RibUnicastEntry(prefixAt(p), std::move(nhs), cands[c].entry, area_, bgpDryRun_,
+                               via);
       }
     }
     throw std::logic_error("AllNodesRouteTable: best candidate not in the selected column");
   }
   if (columnKind(p) == 1) {
     // selectEcmpBgp (Decision.cpp:805-866): the host-side selection's best
-    const BgpSel& b = *bgp_[p];
-    return RibUnicastEntry(prefixes_[p], std::move(nhs), b.bestEntry, b.bestArea, bgpDryRun_,
+    const BgpSel& b = bgpAt(p);
+    return RibUnicastEntry(prefixAt(p), std::move(nhs), b.bestEntry, b.bestArea, bgpDryRun_,
                            b.bestNexthop);
   }
   const thrift::PrefixEntry* bestEntry = nullptr;
@@ -908,7 +925,7 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
       const auto& news = annsAt(p);
       if (columnKind(p) == 1) {
         dirtyAnn.push_back(SPF_MAP_NONE);
-        if (!sameSelection(*bgp_[p], *older.bgp_[pa])) {
+        if (!sameSelection(bgpAt(p), older.bgpAt(pa))) {
           for (const auto& a : news) {
             dirtyAnn.push_back(a.id);
           }
@@ -936,7 +953,7 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
             const auto& o = olds[b];
             if (nodeOf[o.id] == a.id &&
                 (!(o.entry == a.entry) ||
-                 (columnKind(p) == 2 && !(sel_[p]->via[c] == older.sel_[pa]->via[b])))) {
+                 (columnKind(p) == 2 && !(selAt(p).via[c] == older.selAt(pa).via[b])))) {
               dirtyAnn.push_back(a.id);
             }
           }
@@ -1033,7 +1050,7 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
 void AllNodesRouteTable::rebuildServed() {
   holes_ = true;
   if (free_.empty()) {
-    free_.assign(prefixes_.size() + spare_, 0);
+    free_.assign(prefixes_.size() + spare_ + spareSel_, 0);
   }
   served_.clear();
   colOfPrefix_.clear();
@@ -1047,7 +1064,7 @@ void AllNodesRouteTable::rebuildServed() {
 
 std::vector<uint32_t> AllNodesRouteTable::applyPrefixChanges(
     const PrefixState& ps, const std::unordered_set<thrift::IpPrefix>& changed) {
-  if (bgpColumns_ || hasBorder_) {
+  if ((bgpColumns_ && !bgpInPlace_) || hasBorder_) {
     throw std::invalid_argument(
         "AllNodesRouteTable::applyPrefixChanges: tables with bgpColumns or borderNodes are "
         "rebuilt (BGP columns and per-area served sets do not move in place)");
@@ -1058,10 +1075,38 @@ std::vector<uint32_t> AllNodesRouteTable::applyPrefixChanges(
   }
   // rescan every changed prefix with the constructor's rules
   static const thrift::PrefixEntries kNoEntries;
-  PrefixScan scan{nullptr, ps, nullptr, false, bgpIgp_};
+  PrefixScan scan{nullptr, ps, nullptr, bgpColumns_, bgpIgp_};
   for (const auto& prefix : changed) {
     auto it = ps.prefixes().find(prefix);
     scan.items.emplace_back(&prefix, it == ps.prefixes().end() ? &kNoEntries : &it->second);
+  }
+  if (bgpColumns_) {
+    // A BGP route holds the loopback of its best announcer
+    // (PrefixState::getLoopbackVias), which is another prefix of that node:
+    // every served BGP prefix with an announcer that announces, or announced,
+    // a changed prefix is rescanned too (an unchanged one patches to no bits)
+    std::unordered_set<std::string> touched;
+    for (const auto& [prefix, entries] : scan.items) {
+      for (const auto& [node, byArea] : *entries) {
+        touched.insert(node);
+      }
+      if (auto it = colOfPrefix_.find(*prefix); it != colOfPrefix_.end()) {
+        for (const auto& a : annsAt(it->second)) {
+          touched.insert(names_[a.id]);
+        }
+      }
+    }
+    for (size_t c = 0; c < numCols(); ++c) {
+      if (!isUni(c) || isFree(c) || columnKind(c) == 0 || changed.count(prefixAt(c))) {
+        continue;
+      }
+      auto it = ps.prefixes().find(prefixAt(c));
+      if (it != ps.prefixes().end() &&
+          std::any_of(it->second.begin(), it->second.end(),
+                      [&](const auto& kv) { return touched.count(kv.first) > 0; })) {
+        scan.items.emplace_back(&it->first, &it->second);
+      }
+    }
   }
   const size_t n = scan.items.size();
   scan.keep.assign(n, 0);
@@ -1072,102 +1117,221 @@ std::vector<uint32_t> AllNodesRouteTable::applyPrefixChanges(
   for (size_t i = 0; i < n; ++i) {
     scanPrefix(scan, i);
   }
-  // classify; nothing is touched before every new prefix has a column
+  if (bgpColumns_ && !bgpIgp_) {
+    dropUnreachableBgp(scan); // (on the resident rows)
+  }
+  // classify; nothing is touched before every new prefix has a column.  A
+  // prefix keeps its column unless it needs the other kind of device column
+  // (selected / unselected): then the old one is emptied and it moves
   std::vector<uint32_t> colFor(n, SPF_MAP_NONE);
-  size_t need = 0;
+  std::vector<uint8_t> moves(n, 0);
+  size_t need = 0, needSel = 0;
   for (size_t i = 0; i < n; ++i) {
+    const bool wantSel = scan.keep[i] == 3;
     auto it = colOfPrefix_.find(*scan.items[i].first);
     if (it != colOfPrefix_.end()) {
       colFor[i] = it->second;
-    } else {
-      need += scan.keep[i] != 0;
+      moves[i] = scan.keep[i] != 0 && selectedColumn(it->second) != wantSel;
+    }
+    if (scan.keep[i] && (colFor[i] == SPF_MAP_NONE || moves[i])) {
+      (wantSel ? needSel : need) += 1;
     }
   }
-  if (need > freeList_.size()) {
+  if (need > freeList_.size() || needSel > freeSelList_.size()) {
     throw std::length_error(
-        "AllNodesRouteTable::applyPrefixChanges: " + std::to_string(need) +
-        " new prefixes, " + std::to_string(freeList_.size()) + " free columns (rebuild the table)");
+        "AllNodesRouteTable::applyPrefixChanges: " + std::to_string(need) + " + " +
+        std::to_string(needSel) + " new prefixes, " + std::to_string(freeList_.size()) + " + " +
+        std::to_string(freeSelList_.size()) +
+        " free columns (unselected + selected; rebuild the table)");
+  }
+  // the listed columns: column, its changed prefix, and whether it serves the
+  // prefix after the call (else it is emptied)
+  struct Listed {
+    uint32_t col;
+    size_t item;
+    bool serve;
+  };
+  std::vector<Listed> listed;
+  std::vector<std::pair<uint32_t, uint32_t>> moved; // (emptied column, column taken) of one prefix
+  std::vector<uint32_t> taken;                      // popped from the free lists
+  for (size_t i = 0; i < n; ++i) {
+    const bool had = colFor[i] != SPF_MAP_NONE;
+    if (!had && !scan.keep[i]) {
+      continue; // not served before or now
+    }
+    if (had && (!scan.keep[i] || moves[i])) {
+      listed.push_back(Listed{colFor[i], i, false});
+    }
+    if (scan.keep[i] && (!had || moves[i])) {
+      // (freed columns lie behind the spare ones: reused first)
+      auto& fl = scan.keep[i] == 3 ? freeSelList_ : freeList_;
+      const uint32_t c = fl.back();
+      fl.pop_back();
+      taken.push_back(c);
+      if (had) {
+        moved.emplace_back(colFor[i], c);
+      }
+      listed.push_back(Listed{c, i, true});
+    } else if (scan.keep[i]) {
+      listed.push_back(Listed{colFor[i], i, true});
+    }
   }
   std::vector<uint32_t> cols, annOff{0}, ann, dirtyOff{0}, dirtyAnn;
-  std::vector<size_t> item; // per listed column: its changed prefix
-  for (size_t i = 0; i < n; ++i) {
-    if (colFor[i] == SPF_MAP_NONE) {
-      if (!scan.keep[i]) {
-        continue; // not served before or now
-      }
-      colFor[i] = freeList_.back(); // (freed columns lie behind the spare ones: reused first)
-      freeList_.pop_back();
-    } else {
-      // kept announcers whose PrefixEntry differs (the rule of diffMapped)
-      for (const auto& a : scan.anns[i]) {
-        for (const auto& o : annsAt(colFor[i])) {
-          if (o.id == a.id && !(o.entry == a.entry)) {
+  std::vector<uint8_t> candFlags;
+  std::vector<uint32_t> selColumns;
+  std::vector<uint64_t> pairOff{0};
+  std::vector<uint16_t> pairCodes;
+  for (const Listed& l : listed) {
+    const size_t i = l.item;
+    const int newKind = (int)scan.keep[i] - 1;
+    static const std::vector<Announcer> kNone;
+    const auto& news = l.serve ? scan.anns[i] : kNone;
+    if (l.serve && !isFree(l.col)) {
+      const auto& olds = annsAt(l.col);
+      const int oldKind = columnKind(l.col);
+      if (oldKind != newKind) {
+        // Open/R <-> host-selected BGP in one column: every route is another one
+        for (const auto& a : news) {
+          dirtyAnn.push_back(a.id);
+        }
+      } else if (newKind == 1) {
+        if (!sameSelection(bgpAt(l.col), *scan.sels[i])) {
+          for (const auto& a : news) {
             dirtyAnn.push_back(a.id);
           }
         }
+      } else {
+        // kept announcers whose PrefixEntry (selected columns: or loopback)
+        // differs (the rule of diffMapped)
+        for (size_t c = 0; c < news.size(); ++c) {
+          for (size_t o = 0; o < olds.size(); ++o) {
+            if (olds[o].id == news[c].id &&
+                (!(olds[o].entry == news[c].entry) ||
+                 (newKind == 2 && !(selAt(l.col).via[o] == scan.selCols[i]->via[c])))) {
+              dirtyAnn.push_back(news[c].id);
+            }
+          }
+        }
+      }
+      if (newKind == 1) {
+        dirtyAnn.push_back(SPF_MAP_NONE); // the cell's own best is no part of its routes
       }
     }
-    cols.push_back(colFor[i]);
-    item.push_back(i);
-    for (const auto& a : scan.anns[i]) { // (empty when the prefix is no longer served)
-      ann.push_back(a.id);
+    if (selectedColumn(l.col)) {
+      selColumns.push_back(l.col);
+      if (l.serve) {
+        const SelCol& sc = *scan.selCols[i];
+        pairCodes.insert(pairCodes.end(), sc.pair.begin(), sc.pair.end());
+      }
+      pairOff.push_back(pairCodes.size());
+    }
+    cols.push_back(l.col);
+    for (size_t c = 0; c < news.size(); ++c) {
+      ann.push_back(news[c].id);
+      candFlags.push_back(newKind == 2 && scan.selCols[i]->via[c] ? 1 : 0);
     }
     annOff.push_back((uint32_t)ann.size());
     dirtyOff.push_back((uint32_t)dirtyAnn.size());
   }
-  // A kept column whose announcer set changed: `best` can move between two
-  // announcers with EQUAL PrefixEntries, which the device reports (best is a
-  // cell word) and getRouteDelta does not (bestPrefixEntry is the same).  The
+  // A kept Open/R column whose announcer set changed: `best` can move between
+  // two announcers with EQUAL PrefixEntries, which the device reports (best is
+  // a cell word) and getRouteDelta does not (bestPrefixEntry is the same).  The
   // cells of those columns are read before and after the patch and such
-  // cells taken out of this call's delta (suppress_).
+  // cells taken out of this call's delta (suppress_).  A kept selected column
+  // likewise: its best can move with the same candidates (other pair codes),
+  // and the route is the same only where the old and the new best candidate
+  // have equal entries AND equal loopbacks and the cell's igp word stayed.
+  // (Host-selected BGP columns do not compare best.)
   const uint32_t V = (uint32_t)names_.size();
-  std::vector<size_t> risk; // indices into cols
+  std::vector<size_t> risk; // indices into listed
   std::vector<std::vector<Announcer>> riskOld;
-  for (size_t k = 0; k < cols.size(); ++k) {
-    const auto& olds = annsAt(cols[k]);
-    const auto& news = scan.anns[item[k]];
-    if (isFree(cols[k]) || news.empty() || olds.empty()) {
+  std::vector<std::vector<std::optional<thrift::NextHopThrift>>> riskOldVia; // (selected columns)
+  bool riskSel = false;
+  for (size_t k = 0; k < listed.size(); ++k) {
+    const Listed& l = listed[k];
+    if (!l.serve || isFree(l.col)) {
+      continue;
+    }
+    const bool plain = columnKind(l.col) == 0 && scan.keep[l.item] == 1;
+    const bool selected = columnKind(l.col) == 2 && scan.keep[l.item] == 3;
+    if (!plain && !selected) {
+      continue;
+    }
+    const auto& olds = annsAt(l.col);
+    const auto& news = scan.anns[l.item];
+    if (news.empty() || olds.empty()) {
       continue;
     }
     bool sameIds = olds.size() == news.size();
     for (size_t c = 0; sameIds && c < news.size(); ++c) {
       sameIds = olds[c].id == news[c].id;
     }
-    if (!sameIds) {
+    // (a selected column: only where some old and some other new candidate
+    // have equal entries and equal loopbacks can a moved best leave the route
+    // equal -- else no cell can be left out and the reads are saved)
+    bool twins = false;
+    for (size_t o = 0; selected && !twins && o < olds.size(); ++o) {
+      for (size_t c = 0; !twins && c < news.size(); ++c) {
+        twins = olds[o].id != news[c].id && olds[o].entry == news[c].entry &&
+            selAt(l.col).via[o] == scan.selCols[l.item]->via[c];
+      }
+    }
+    if (selected ? twins : !sameIds) {
       risk.push_back(k);
       riskOld.push_back(olds);
+      riskOldVia.push_back(selected ? selAt(l.col).via
+                                    : std::vector<std::optional<thrift::NextHopThrift>>{});
+      riskSel |= selected;
     }
   }
   struct CellList {
-    std::vector<uint32_t> metric, best, lmet;
+    std::vector<uint32_t> metric, best, lmet, igp;
     std::vector<uint64_t> links;
   };
-  std::vector<uint32_t> riskRows, riskCols;
-  uint64_t riskLw = 0, riskLm = 0;
-  for (uint32_t i = 0; !risk.empty() && i < V; ++i) {
-    const uint64_t deg = row_[i + 1] - row_[i];
-    for (const size_t k : risk) {
-      riskRows.push_back(i);
-      riskCols.push_back(cols[k]);
-      riskLw += (deg + 63) / 64;
-      riskLm += lfa_ ? deg : 0;
-    }
-  }
-  auto readRisk = [&]() {
+  // the cells (every row) x (the given columns), row-major
+  auto readCells = [&](const std::vector<uint32_t>& cs) {
     CellList c;
-    c.metric.resize(riskRows.size());
-    c.best.resize(riskRows.size());
-    c.links.resize(std::max<uint64_t>(riskLw, 1));
-    c.lmet.resize(std::max<uint64_t>(riskLm, 1));
+    std::vector<uint32_t> rows, ccols;
+    uint64_t lw = 0, lm = 0;
+    for (uint32_t i = 0; i < V; ++i) {
+      const uint64_t deg = row_[i + 1] - row_[i];
+      for (const uint32_t x : cs) {
+        rows.push_back(i);
+        ccols.push_back(x);
+        lw += (deg + 63) / 64;
+        lm += lfa_ ? deg : 0;
+      }
+    }
+    c.metric.resize(rows.size());
+    c.best.resize(rows.size());
+    c.links.resize(std::max<uint64_t>(lw, 1));
+    c.lmet.resize(std::max<uint64_t>(lm, 1));
     if (int s = spf_route_table_fetch_cells(
-            table_.get(), riskRows.size(), riskRows.data(), riskCols.data(), c.metric.data(),
-            c.best.data(), c.links.data(), lfa_ ? c.lmet.data() : nullptr);
+            table_.get(), rows.size(), rows.data(), ccols.data(), c.metric.data(), c.best.data(),
+            c.links.data(), lfa_ ? c.lmet.data() : nullptr);
         s != SPF_OK) {
       tableFailure("spf_route_table_fetch_cells", s);
     }
+    if (riskSel) {
+      c.igp.resize(rows.size());
+      if (int s = spf_route_table_fetch_cells_igp(table_.get(), rows.size(), rows.data(),
+                                                  ccols.data(), c.igp.data());
+          s != SPF_OK) {
+        tableFailure("spf_route_table_fetch_cells_igp", s);
+      }
+    }
     return c;
   };
-  const CellList riskBefore = risk.empty() ? CellList{} : readRisk();
+  std::vector<uint32_t> riskCols, movedFrom, movedTo;
+  for (const size_t k : risk) {
+    riskCols.push_back(listed[k].col);
+  }
+  for (const auto& [from, to] : moved) {
+    movedFrom.push_back(from);
+    movedTo.push_back(to);
+  }
+  const CellList riskBefore = risk.empty() ? CellList{} : readCells(riskCols);
+  const CellList movedBefore = moved.empty() ? CellList{} : readCells(movedFrom);
   spf_route_patch patch{};
   patch.num_columns = (uint32_t)cols.size();
   patch.columns = cols.data();
@@ -1175,22 +1339,31 @@ std::vector<uint32_t> AllNodesRouteTable::applyPrefixChanges(
   patch.announcers = ann.data();
   patch.dirty_off = dirtyAnn.empty() ? nullptr : dirtyOff.data();
   patch.dirty_ann = dirtyAnn.data();
+  spf_route_select_desc sd{};
+  sd.num_selected = (uint32_t)selColumns.size();
+  sd.columns = selColumns.data();
+  sd.pair_offsets = pairOff.data();
+  sd.pair_codes = pairCodes.data();
+  candFlags.push_back(0); // (never a null array)
+  sd.cand_flags = candFlags.data();
   std::vector<uint32_t> counts(names_.size());
-  if (int s = spf_route_table_patch_columns(table_.get(), &patch, counts.data()); s != SPF_OK) {
+  const int st = bgpColumns_
+      ? spf_route_table_patch_columns_sel(table_.get(), &patch, selColumns.empty() ? nullptr : &sd,
+                                          counts.data())
+      : spf_route_table_patch_columns(table_.get(), &patch, counts.data());
+  if (st != SPF_OK) {
     // (the engine checked before it touched anything: give the columns back)
-    for (size_t k = cols.size(); k-- > 0;) {
-      if (isFree(cols[k])) {
-        freeList_.push_back(cols[k]);
-      }
+    for (size_t k = taken.size(); k-- > 0;) {
+      (selectedColumn(taken[k]) ? freeSelList_ : freeList_).push_back(taken[k]);
     }
-    tableFailure("spf_route_table_patch_columns", s);
+    tableFailure("spf_route_table_patch_columns", st);
   }
   if (int s = spf_route_table_patch_elapsed_ms(table_.get(), &patchMs_); s != SPF_OK) {
     tableFailure("spf_route_table_patch_elapsed_ms", s);
   }
   suppress_.assign(V, {});
   if (!risk.empty()) {
-    const CellList after = readRisk();
+    const CellList after = readCells(riskCols);
     auto entryOf = [](const std::vector<Announcer>& as, uint32_t id) -> const thrift::PrefixEntry* {
       for (const auto& a : as) {
         if (a.id == id) {
@@ -1208,12 +1381,31 @@ std::vector<uint32_t> AllNodesRouteTable::applyPrefixChanges(
         if (riskBefore.metric[x] == 0xFFFFFFFFu || after.metric[x] == 0xFFFFFFFFu || ob == nb) {
           continue;
         }
-        const auto& news = scan.anns[item[risk[r]]];
+        const auto& news = scan.anns[listed[risk[r]].item];
         const auto* oe = entryOf(riskOld[r], ob);
         const auto* ne = entryOf(news, nb);
-        const auto* neOld = entryOf(riskOld[r], nb); // (the new best, if it was an announcer: dirty?)
-        if (!oe || !ne || !(*oe == *ne) || (neOld && !(*neOld == *ne))) {
+        if (!oe || !ne || !(*oe == *ne)) {
           continue;
+        }
+        if (!riskOldVia[r].empty()) {
+          // a selected column: the best candidate's loopback and the igp word
+          // are the route's bestNexthop
+          const auto& nvia = scan.selCols[listed[risk[r]].item]->via;
+          size_t oi = 0, ni = 0; // (oe and ne were found: both ids are in their lists)
+          while (riskOld[r][oi].id != ob) {
+            ++oi;
+          }
+          while (news[ni].id != nb) {
+            ++ni;
+          }
+          if (!(riskOldVia[r][oi] == nvia[ni]) || riskBefore.igp[x] != after.igp[x]) {
+            continue;
+          }
+        } else {
+          const auto* neOld = entryOf(riskOld[r], nb); // (the new best, if it was an announcer: dirty?)
+          if (neOld && !(*neOld == *ne)) {
+            continue;
+          }
         }
         if ((!lfa_ && riskBefore.metric[x] != after.metric[x]) ||
             !std::equal(after.links.begin() + lw, after.links.begin() + lw + W,
@@ -1222,35 +1414,60 @@ std::vector<uint32_t> AllNodesRouteTable::applyPrefixChanges(
                         riskBefore.lmet.begin() + lm)) {
           continue;
         }
-        suppress_[i].push_back(cols[risk[r]]); // only `best` moved, onto an equal entry
+        suppress_[i].push_back(riskCols[r]); // only `best` moved, onto an equal entry
       }
-      std::sort(suppress_[i].begin(), suppress_[i].end());
-      counts[i] -= (uint32_t)suppress_[i].size();
     }
   }
-  // the host's view of the columns
-  for (size_t k = 0; k < cols.size(); ++k) {
-    const uint32_t c = cols[k];
-    const size_t i = item[k];
-    const bool now = scan.keep[i] != 0;
-    if (!now && !isFree(c)) {
-      freeList_.push_back(c);
+  if (!moved.empty()) {
+    // a prefix that moved to the other kind of column: a node with a route
+    // before and after gets ONE update (getRouteDelta), so the emptied
+    // column's delete is taken out there
+    const CellList after = readCells(movedTo);
+    size_t x = 0;
+    for (uint32_t i = 0; i < V; ++i) {
+      for (size_t r = 0; r < moved.size(); ++r, ++x) {
+        if (movedBefore.metric[x] != 0xFFFFFFFFu && after.metric[x] != 0xFFFFFFFFu) {
+          suppress_[i].push_back(movedFrom[r]);
+        }
+      }
     }
-    free_[slotOf(c)] = now ? 0 : 1;
+  }
+  for (uint32_t i = 0; i < V; ++i) {
+    std::sort(suppress_[i].begin(), suppress_[i].end());
+    counts[i] -= (uint32_t)suppress_[i].size();
+  }
+  // the host's view of the columns (emptied ones first: a moved prefix's new
+  // column is listed after its old one)
+  for (const Listed& l : listed) {
+    const uint32_t c = l.col;
+    const size_t i = l.item, slot = slotOf(c);
+    if (!l.serve) {
+      (selectedColumn(c) ? freeSelList_ : freeList_).push_back(c);
+    }
+    free_[slot] = l.serve ? 0 : 1;
     // (a freed column keeps its prefix: this call's delta names it in the delete)
-    if (c < prefixes_.size()) {
-      if (now) {
-        prefixes_[c] = *scan.items[i].first;
-      }
-      announcers_[c] = std::move(scan.anns[i]);
+    auto& as = c < prefixes_.size() ? announcers_[c] : spareAnn_[c - spareBase()];
+    if (l.serve) {
+      (c < prefixes_.size() ? prefixes_[c] : sparePrefix_[c - spareBase()]) = *scan.items[i].first;
+      as = std::move(scan.anns[i]);
     } else {
-      if (now) {
-        sparePrefix_[c - spareBase()] = *scan.items[i].first;
-      }
-      spareAnn_[c - spareBase()] = std::move(scan.anns[i]);
+      as.clear();
+    }
+    if (slot < bgp_.size()) {
+      bgp_[slot] = l.serve && scan.keep[i] == 2 ? std::move(scan.sels[i]) : std::nullopt;
+      sel_[slot] = l.serve && scan.keep[i] == 3 ? std::move(scan.selCols[i]) : std::nullopt;
     }
   }
   rebuildServed();
+  if (bgpColumns_) {
+    nbgp_ = nsel_ = 0;
+    for (size_t c = 0; c < numCols(); ++c) {
+      if (isUni(c) && !isFree(c)) {
+        nbgp_ += columnKind(c) >= 1;
+        nsel_ += columnKind(c) == 2;
+      }
+    }
+  }
   diffed_ = true;
   mapped_ = false;
   patchDelta_ = true;
@@ -1439,7 +1656,7 @@ uint64_t AllNodesRouteTable::deltaFetchBytes(const std::string& node) const {
     const uint64_t C = t.numCols();
     const uint64_t deg = t.row_[r + 1] - t.row_[r];
     // (tables with selected columns: the row's igp and winners words too)
-    return C * (8 + ((deg + 63) / 64) * 8 + (t.lfa_ ? deg * 4 : 0)) + (uint64_t)t.nsel_ * 8;
+    return C * (8 + ((deg + 63) / 64) * 8 + (t.lfa_ ? deg * 4 : 0)) + (uint64_t)t.devSel_ * 8;
   };
   const uint64_t C = numCols();
   uint64_t b = ((C + 63) / 64) * 8 + rowBytes(*this, i);
@@ -1482,8 +1699,8 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
     tableFailure("spf_route_table_delta_fetch", s);
   }
   // selected columns: the igp lane of the packed list (bestNexthop.metric)
-  std::vector<uint32_t> igp(nsel_ ? z.cells : 0);
-  if (nsel_) {
+  std::vector<uint32_t> igp(devSel_ ? z.cells : 0);
+  if (devSel_) {
     if (int s = spf_route_table_delta_fetch_igp(table_.get(), igp.data()); s != SPF_OK) {
       tableFailure("spf_route_table_delta_fetch_igp", s);
     }
@@ -1595,7 +1812,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
     const Row r = k1 > k0
         ? view(*this, i, col.data() + k0, metric.data() + k0, best.data() + k0, (size_t)(k1 - k0),
                links.data() + lwBase[i], lmet.data() + lmBase[i],
-               nsel_ ? igp.data() + k0 : nullptr)
+               devSel_ ? igp.data() + k0 : nullptr)
         : Row{};
     if (patchDelta_ && !suppress_[i].empty()) {
       std::vector<uint32_t> keep;
@@ -1640,7 +1857,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
   // what crossed from the device: the pack's totals, the packed list, and per
   // gathered cell its metric and best, plus the link words and link metrics
   // (tables with selected columns: the igp lane, one more word per cell)
-  st.bytes = 32 + 2 * ((uint64_t)V + 1) * 8 + z.cells * (nsel_ ? 16 : 12) + z.link_words * 8 +
+  st.bytes = 32 + 2 * ((uint64_t)V + 1) * 8 + z.cells * (devSel_ ? 16 : 12) + z.link_words * 8 +
       z.link_metrics * 4 + z.gone * 4 + (st.newerCells + st.olderCells) * 8 +
       (cn.links.size() + co.links.size()) * 8 + (cn.lmet.size() + co.lmet.size()) * 4;
   lastDeltas_ = st;

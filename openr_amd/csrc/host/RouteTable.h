@@ -89,10 +89,17 @@ class AllNodesRouteTable {
   // Left to the host: more than 32 candidates, a candidate vector with a
   // foreign entity of priority 3500 (its order against the IGP entity is
   // std::sort's), entries in another area.
+  // bgpInPlace (with bgpColumns): applyPrefixChanges serves BGP columns too
+  // (spf_route_table_patch_columns_sel).  Off by default only because a test
+  // pins the refusal of bgpColumns tables.
+  // spareSelectedColumns (with bgpUseIgpMetric, else ignored): that many empty
+  // SELECTED columns after the spare columns, for BGP prefixes announced later
+  // (a column's kind is fixed when the device table is created).
   AllNodesRouteTable(
       const LinkState& ls, const PrefixState& ps, bool enableV4 = true, bool computeLfa = false,
       const std::unordered_set<std::string>* borderNodes = nullptr, bool bgpColumns = false,
-      bool bgpDryRun = false, bool bgpUseIgpMetric = false, size_t spareColumns = 0);
+      bool bgpDryRun = false, bool bgpUseIgpMetric = false, size_t spareColumns = 0,
+      bool bgpInPlace = false, size_t spareSelectedColumns = 0);
   ~AllNodesRouteTable();
   AllNodesRouteTable(const AllNodesRouteTable&) = delete;
   AllNodesRouteTable& operator=(const AllNodesRouteTable&) = delete;
@@ -198,9 +205,19 @@ class AllNodesRouteTable {
   //     earlier call first, else a spare one.  Too few: std::length_error
   //     before anything is touched (rebuild the table).
   // Throws std::invalid_argument, before anything is touched, on a table built
-  // with bgpColumns or borderNodes (BGP columns in place and AllAreasRouteTable
-  // are not covered; without bgpColumns a BGP prefix is not served and takes
-  // no column).  Afterwards prefixes(), routes(), countRoutes() describe the
+  // with borderNodes, or with bgpColumns and without bgpInPlace (without
+  // bgpColumns a BGP prefix is not served and takes no column).
+  // bgpInPlace: a host-selected BGP column gets the new selection's winners
+  // (SPF_MAP_NONE in its dirty list: best is not compared; every announcer
+  // dirty when the best entry or loopback differs), a selected column its new
+  // candidates, pair codes and loopback flags (candidates whose entry or
+  // loopback differs are dirty) -- new ones in a free selected column.  A
+  // prefix whose kind changes between unselected kinds keeps its column (every
+  // announcer dirty); between a selected and an unselected column it moves,
+  // and a node with a route on both sides gets one update.  In a selected
+  // column best (its entry and loopback) is part of the route: a cell whose
+  // best alone moved is left out only where the old and the new best
+  // candidate have equal entries and equal loopbacks and the igp word stayed.  Afterwards prefixes(), routes(), countRoutes() describe the
   // new state and changedSplit / delta / deltas the delta of this call, from
   // the new cells alone (no older table; the MPLS lists are empty: label
   // columns do not move).  A cell whose best announcer alone moved, between
@@ -210,6 +227,8 @@ class AllNodesRouteTable {
       const PrefixState& ps, const std::unordered_set<thrift::IpPrefix>& changed);
   // columns applyPrefixChanges can still give away
   size_t freeColumns() const { return freeList_.size(); }
+  // free selected columns (spareSelectedColumns and freed ones)
+  size_t freeSelectedColumns() const { return freeSelList_.size(); }
   // device time of the last applyPrefixChanges (bitmap clear + spf_route_patch_kernel)
   float patchMs() const { return patchMs_; }
   // BGP prefixes among them (bgpColumns), selected columns included
@@ -295,20 +314,20 @@ class AllNodesRouteTable {
   std::vector<std::shared_ptr<Link>> halfLink_; // half-edge -> Link
   std::vector<thrift::IpPrefix> prefixes_;
   std::vector<std::vector<Announcer>> announcers_;
-  std::vector<std::optional<BgpSel>> bgp_; // per prefix (set: a BGP column)
+  std::vector<std::optional<BgpSel>> bgp_; // per unicast slot (set: a BGP column)
   // a selected column (bgpUseIgpMetric): parallel to the column's announcers_
   // (= candidates, fold order)
   struct SelCol {
     std::vector<uint16_t> pair; // spf_route_select_desc::pair_codes of the column
     std::vector<std::optional<thrift::NextHopThrift>> via; // the candidate's one loopback via
   };
-  std::vector<std::optional<SelCol>> sel_; // per prefix
+  std::vector<std::optional<SelCol>> sel_; // per unicast slot
   // The constructor's steps, in call order.  PrefixScan: what the constructor
   // was given and, per prefix of PrefixState in map order, what scanPrefix
   // found (keep: 0 not served, 1 Open/R, 2 BGP selected on the host, 3 a
   // selected column).
   struct PrefixScan {
-    const LinkState* ls; // (null in applyPrefixChanges: read for bgpColumns only)
+    const LinkState* ls; // (null in applyPrefixChanges: overloaded_ answers instead)
     const PrefixState& ps;
     const std::unordered_set<std::string>* borderNodes;
     bool bgpColumns, bgpUseIgpMetric;
@@ -323,6 +342,13 @@ class AllNodesRouteTable {
   };
   void scanPrefix(PrefixScan& s, size_t i) const;
   void dropUnreachableBgp(PrefixScan& s) const;
+  // announcer id -> every node reaches it (one row fetch each, kept for
+  // applyPrefixChanges: valid for the table's life since the rows are the
+  // snapshot's; at most one entry per node).  Filled from the const
+  // dropUnreachableBgp, which only the constructor and applyPrefixChanges
+  // call: the object is not safe for concurrent use with applyPrefixChanges,
+  // the const accessors do not touch it.
+  mutable std::unordered_map<uint32_t, bool> reachesAll_;
   // annOff / ann: the announcer lists of every column, as the engine takes them
   void orderColumns(std::vector<uint32_t>& annOff, std::vector<uint32_t>& ann);
   void addNodeLabelColumns(
@@ -330,18 +356,31 @@ class AllNodesRouteTable {
   void collectAdjLabels(const LinkState& ls);
   void createAndRunTable(const std::vector<uint32_t>& annOff, const std::vector<uint32_t>& ann);
   size_t nbgp_{0}, nsel_{0};
-  bool bgpColumns_{false}, bgpDryRun_{false}, bgpIgp_{false};
-  // 0 Open/R, 1 BGP selected on the host, 2 a selected column
-  // (a spare column is an Open/R one)
-  int columnKind(size_t p) const {
-    return p >= prefixes_.size() ? 0 : sel_[p] ? 2 : bgp_[p] ? 1 : 0;
+  size_t devSel_{0}; // selected columns of the device table (spare ones included)
+  bool bgpColumns_{false}, bgpDryRun_{false}, bgpIgp_{false}, bgpInPlace_{false};
+  std::vector<uint8_t> overloaded_; // per node id, from the snapshot (scanPrefix without LinkState)
+  // 0 Open/R, 1 BGP selected on the host, 2 a selected column -- by what the
+  // column serves (a free column is an Open/R one)
+  int columnKind(size_t c) const {
+    if (!isUni(c) || slotOf(c) >= sel_.size()) {
+      return 0;
+    }
+    return sel_[slotOf(c)] ? 2 : bgp_[slotOf(c)] ? 1 : 0;
   }
+  // the device column is a selected one (fixed at creation)
+  bool selectedColumn(size_t c) const {
+    return c < prefixes_.size() ? ctorSel_[c] != 0 : c >= spareBase() + spare_;
+  }
+  std::vector<uint8_t> ctorSel_; // per constructor column: created as a selected column
+  const SelCol& selAt(size_t c) const { return *sel_[slotOf(c)]; }
+  const BgpSel& bgpAt(size_t c) const { return *bgp_[slotOf(c)]; }
   // Column layout: [0, prefixes_.size()) the constructor's unicast columns,
-  // then owners_.size() node-label columns, then spare_ spare columns.  A
-  // unicast column has a slot: its index, or prefixes_.size() + j for spare
-  // column j.  free_[slot]: the column serves no prefix (its prefix entry is
+  // then owners_.size() node-label columns, then spare_ spare columns, then
+  // spareSel_ spare selected columns.  A unicast column has a slot: its index,
+  // or prefixes_.size() + j for spare column j (of either kind).  free_[slot]: the column serves no prefix (its prefix entry is
   // the last one it served, read by the delete of that call's delta).
-  size_t spare_{0};
+  size_t spare_{0}, spareSel_{0};
+  std::vector<uint32_t> freeSelList_; // free selected columns, taken from the back
   std::vector<thrift::IpPrefix> sparePrefix_;
   std::vector<std::vector<Announcer>> spareAnn_;
   std::vector<uint8_t> free_;
@@ -358,7 +397,7 @@ class AllNodesRouteTable {
   bool suppressed(uint32_t i, uint32_t c) const {
     return patchDelta_ && std::binary_search(suppress_[i].begin(), suppress_[i].end(), c);
   }
-  size_t numCols() const { return prefixes_.size() + owners_.size() + spare_; }
+  size_t numCols() const { return prefixes_.size() + owners_.size() + spare_ + spareSel_; }
   size_t spareBase() const { return prefixes_.size() + owners_.size(); }
   bool isUni(size_t c) const { return c < prefixes_.size() || c >= spareBase(); }
   size_t slotOf(size_t c) const { return c < prefixes_.size() ? c : c - owners_.size(); }

@@ -478,15 +478,20 @@ PYBIND11_MODULE(_openr_spf, m) {
   py::class_<AllNodesRouteTable>(m, "AllNodesRouteTable")
       .def(py::init([](const AreaMapHolder& areas, const std::string& area, const PrefixState& ps,
                        bool enableV4, bool lfa, bool bgpColumns, bool bgpDryRun,
-                       bool bgpUseIgpMetric, size_t spareColumns) {
-             return std::make_unique<AllNodesRouteTable>(areas.map.at(area), ps, enableV4, lfa,
-                                                         nullptr, bgpColumns, bgpDryRun,
-                                                         bgpUseIgpMetric, spareColumns);
+                       bool bgpUseIgpMetric, size_t spareColumns, bool bgpInPlace,
+                       size_t spareSelectedColumns,
+                       const std::optional<std::unordered_set<std::string>>& borderNodes) {
+             // (borderNodes is read by the constructor only)
+             return std::make_unique<AllNodesRouteTable>(
+                 areas.map.at(area), ps, enableV4, lfa, borderNodes ? &*borderNodes : nullptr,
+                 bgpColumns, bgpDryRun, bgpUseIgpMetric, spareColumns, bgpInPlace,
+                 spareSelectedColumns);
            }),
            py::arg("areas"), py::arg("area"), py::arg("prefix_state"), py::arg("enable_v4") = true,
            py::arg("lfa") = false, py::arg("bgp_columns") = false, py::arg("bgp_dry_run") = false,
            py::arg("bgp_use_igp_metric") = false, py::arg("spare_columns") = 0,
-           py::keep_alive<1, 2>())
+           py::arg("bgp_in_place") = false, py::arg("spare_selected_columns") = 0,
+           py::arg("border_nodes") = py::none(), py::keep_alive<1, 2>())
       .def("apply_prefix_changes",
            [](AllNodesRouteTable& t, const PrefixState& ps, const py::iterable& prefixes) {
              // prefixes: the keys updatePrefixDatabase returns, (address bytes, length)
@@ -502,6 +507,7 @@ PYBIND11_MODULE(_openr_spf, m) {
            },
            py::arg("prefix_state"), py::arg("prefixes"))
       .def_property_readonly("free_columns", &AllNodesRouteTable::freeColumns)
+      .def_property_readonly("free_selected_columns", &AllNodesRouteTable::freeSelectedColumns)
       .def_property_readonly("patch_ms", &AllNodesRouteTable::patchMs)
       .def_property_readonly("num_nodes", &AllNodesRouteTable::numNodes)
       .def_property_readonly("num_prefixes", &AllNodesRouteTable::numPrefixes)

@@ -6498,16 +6498,34 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
 // not shared with it: called from there, even force-inlined and with the
 // output pointers derived at the same point, it cost both instances a VGPR
 // and SGPR spills.  A change of the cell goes into both.
-template <class Where>
+// SEL (the <.., true> patch instances): as in spf_route_table_kernel<true>, a
+// selected column (selc) takes best = sbest and only the announcers in its
+// winners word wm; wm = ~0u otherwise.  With SEL false the three arguments are
+// unused and the instance is the cell as it was.
+template <bool SEL, class Where>
 __device__ __forceinline__ void rt_cell(
     const RouteTableArgs& a, uint32_t q, uint32_t p, uint32_t s, const uint32_t* d,
     const uint8_t* nhq, uint32_t W, uint32_t NB, uint32_t e0, uint32_t deg, uint32_t WL,
     bool staged, const uint32_t* st_nbr, const uint32_t* st_w, const uint32_t* st_slot,
-    const uint32_t* st_slotall, const uint32_t* st_dns, Where&& where) {
+    const uint32_t* st_slotall, const uint32_t* st_dns, [[maybe_unused]] bool selc,
+    [[maybe_unused]] uint32_t wm, [[maybe_unused]] uint32_t sbest, Where&& where) {
   const uint32_t lo = a.ann_off[p], hi = a.ann_off[p + 1];
   bool self = false;
   uint32_t best = kInf32, reach = 0, undrained = 0;
-  for (uint32_t i = lo; i < hi; ++i) {
+  if constexpr (SEL) {
+    if (selc) {
+      best = sbest;
+      reach = wm != 0; // winners are reachable; self and drained: decided by the fold
+    }
+  }
+  auto in_w = [&](uint32_t i) -> bool {
+    if constexpr (SEL) {
+      return (wm >> ((i - lo) & 31u)) & 1u;
+    } else {
+      return true;
+    }
+  };
+  for (uint32_t i = lo; i < hi && !(SEL && selc); ++i) {
     const uint32_t x = a.ann[i];
     self |= x == s;
     if (d[x] == kInf32) {
@@ -6535,7 +6553,7 @@ __device__ __forceinline__ void rt_cell(
   uint32_t mn = kInf32;
   for (uint32_t i = lo; i < hi; ++i) {
     const uint32_t x = a.ann[i];
-    if (d[x] != kInf32 && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+    if (d[x] != kInf32 && in_w(i) && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
       mn = min(mn, d[x]);
     }
   }
@@ -6551,7 +6569,7 @@ __device__ __forceinline__ void rt_cell(
     }
     for (uint32_t i = lo; i < hi; ++i) {
       const uint32_t x = a.ann[i];
-      if (d[x] == mn && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+      if (d[x] == mn && in_w(i) && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
 #pragma unroll
         for (uint32_t k = 0; k < kRtMaskWords; ++k) {
           if (k < W) {
@@ -6581,7 +6599,8 @@ __device__ __forceinline__ void rt_cell(
           const uint64_t lim = (uint64_t)mn + st_dns[j];
           for (uint32_t i = lo; i < hi; ++i) {
             const uint32_t x = a.ann[i];
-            if (d[x] == kInf32 || (filt && !((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+            if (d[x] == kInf32 || !in_w(i) ||
+                (filt && !((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
               continue;
             }
             const uint32_t dx = rn[x];
@@ -6630,7 +6649,7 @@ __device__ __forceinline__ void rt_cell(
       uint64_t mm = 0;
       for (uint32_t i = lo; i < hi && !mm; ++i) {
         const uint32_t x = a.ann[i];
-        if (d[x] == mn && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
+        if (d[x] == mn && in_w(i) && (!filt || ((a.trbits[x >> 5] >> (x & 31)) & 1u))) {
           mm = (nh_load(nhq, NB, W, x, sl >> 6) >> (sl & 63)) & 1ull;
         }
       }
@@ -6693,8 +6712,87 @@ struct RoutePatchArgs {
   uint32_t nrows, k, pw, routes_only;
 };
 
-template <uint32_t RPW>
-__global__ __launch_bounds__(256) void spf_route_patch_kernel(RoutePatchArgs pa) {
+// The <RPW, true> instances (spf_route_table_patch_columns_sel) take the
+// listed columns that the instances above cannot: selected columns, and
+// unselected ones whose dirty list holds kInf32 (SPF_MAP_NONE: best is not
+// compared, the rule of the mapped diff).  For a selected column the lane
+// that owns it first folds the column's NEW candidates over the row's
+// distances (rt_fold), then computes the cell over the winners word
+// (rt_cell<true>) in the same pass: winners, best and igp stay in registers
+// between the two.  A cell with a route before and after whose igp word
+// differs is changed too; the row's [S] selection words are overwritten where
+// they differ.  t.sel_of is null in a table without selected columns.
+struct RoutePatchSelArgs : RoutePatchArgs {
+  const uint64_t* pair_off; // [S + 1] the patched pair tables
+  const uint16_t* pair;
+  const uint8_t* cflags;    // parallel to t.ann
+  uint32_t* sel_w;          // [nq][S] resident selection words
+  uint32_t* sel_best;
+  uint32_t* sel_igp;
+};
+
+enum : uint32_t {
+  kCmpWinner = 0, // MetricVectorUtils::CompareResult, in its order
+  kCmpTieWinner = 1,
+  kCmpTie = 2,
+  kCmpTieLooser = 3,
+  kCmpLooser = 4,
+  kCmpError = 5
+};
+// spf_route_select_kernel's fold of one (row, selected column) for the patch:
+// candidates ann[lo .. lo + n) against pair table pt.  A COPY of that kernel's
+// loop body (its comment has the rule), kept apart like rt_cell.  wm = the
+// drain-filtered winners word (0: no route), best = the fold's best
+// candidate's node, igp = min d over the reachable candidates; kInf32 both
+// without a route.
+__device__ __forceinline__ void rt_fold(
+    const RouteTableArgs& a, const uint16_t* pt, const uint8_t* cflags, uint32_t s,
+    const uint32_t* d, uint32_t lo, uint32_t n, uint32_t& wm, uint32_t& sbest, uint32_t& sigp) {
+  uint32_t best = kInf32, dbest = 0, igp = kInf32;
+  uint32_t mask = 0, trm = 0, selfm = 0;
+  bool ok = true;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t x = a.ann[lo + i];
+    const uint32_t dx = d[x];
+    if (dx == kInf32) {
+      continue;
+    }
+    igp = min(igp, dx);
+    trm |= ((a.trbits[x >> 5] >> (x & 31)) & 1u) << i;
+    selfm |= (uint32_t)(x == s) << i;
+    uint32_t code = kCmpWinner;
+    if (best != kInf32) {
+      const uint32_t e = pt[i * (i - 1) / 2 + best];
+      code = (e >> (dx < dbest ? 0u : dx == dbest ? 3u : 6u)) & 7u;
+    }
+    if (code == kCmpTie || code >= kCmpError) {
+      ok = false;
+      break;
+    }
+    if (code == kCmpWinner) {
+      mask = 0;
+    }
+    if (code <= kCmpTieWinner) {
+      best = i;
+      dbest = dx;
+    }
+    if (code <= kCmpTieLooser) {
+      mask |= 1u << i;
+    }
+  }
+  const uint32_t filt = (mask & trm) ? (mask & trm) : mask;
+  bool route = ok && filt != 0 && !(filt & selfm); // (filt != 0: best is a candidate)
+  if (route) {
+    route = cflags[lo + best] & 1u;
+  }
+  wm = route ? filt : 0u;
+  sbest = route ? a.ann[lo + best] : kInf32;
+  sigp = route ? igp : kInf32;
+}
+
+template <uint32_t RPW, bool SEL = false>
+__global__ __launch_bounds__(256) void spf_route_patch_kernel(
+    std::conditional_t<SEL, RoutePatchSelArgs, RoutePatchArgs> pa) {
   constexpr uint32_t kStage = kRtStage / RPW, kLanes = 256 / RPW;
   __shared__ uint32_t st_nbr[kRtStage];
   __shared__ uint32_t st_w[kRtStage];
@@ -6735,13 +6833,25 @@ __global__ __launch_bounds__(256) void spf_route_patch_kernel(RoutePatchArgs pa)
     uint32_t nm, nbest;
     uint64_t* nl = slk + (size_t)kk * WL;
     uint32_t* nlm = slm ? slm + (size_t)kk * deg : nullptr;
-    rt_cell(a, q, p, s, d, nhq, W, NB, e0, deg, WL, staged, nbr, w, slot, slotall, dns,
-                   [&](uint32_t*& metric_o, uint32_t*& best_o, uint64_t*& lkp, uint32_t*& lm) {
-                     metric_o = &nm;
-                     best_o = &nbest;
-                     lkp = nl;
-                     lm = nlm;
-                   });
+    [[maybe_unused]] bool selc = false;
+    [[maybe_unused]] uint32_t wm = ~0u, sbest = kInf32, sigp = kInf32, ks = kInf32;
+    if constexpr (SEL) {
+      ks = a.sel_of ? a.sel_of[p] : kInf32;
+      if (ks != kInf32) {
+        selc = true;
+        const uint32_t lo = a.ann_off[p];
+        rt_fold(a, pa.pair + pa.pair_off[ks], pa.cflags, s, d, lo, a.ann_off[p + 1] - lo, wm,
+                sbest, sigp);
+      }
+    }
+    rt_cell<SEL>(a, q, p, s, d, nhq, W, NB, e0, deg, WL, staged, nbr, w, slot, slotall, dns, selc,
+                 wm, sbest,
+                 [&](uint32_t*& metric_o, uint32_t*& best_o, uint64_t*& lkp, uint32_t*& lm) {
+                   metric_o = &nm;
+                   best_o = &nbest;
+                   lkp = nl;
+                   lm = nlm;
+                 });
     const size_t o = (size_t)q * a.P + p;
     uint64_t* ol = lk + (size_t)p * WL;
     uint32_t* olm = slm ? a.lmet_out + a.lm_off[q] + (size_t)p * deg : nullptr;
@@ -6751,12 +6861,33 @@ __global__ __launch_bounds__(256) void spf_route_patch_kernel(RoutePatchArgs pa)
       ch = om != nm;
     } else {
       bool dirty = false;
+      [[maybe_unused]] bool anyBest = false;
       if (pa.dirty_off) {
         for (uint32_t i = pa.dirty_off[kk], e = pa.dirty_off[kk + 1]; i < e; ++i) {
+          if constexpr (SEL) {
+            anyBest |= pa.dirty_ann[i] == kInf32;
+          }
           dirty |= pa.dirty_ann[i] == nbest;
         }
       }
-      ch = (om != nm && !pa.routes_only) || ob != nbest || dirty;
+      ch = (om != nm && !pa.routes_only) || (ob != nbest && !(SEL && anyBest)) || dirty;
+    }
+    if constexpr (SEL) {
+      if (selc) {
+        const size_t os = (size_t)q * a.S + ks;
+        const uint32_t oigp = pa.sel_igp[os];
+        // (igp is kInf32 exactly where the metric is: with one side routeless ch is set)
+        ch = ch || oigp != sigp;
+        if (oigp != sigp) {
+          pa.sel_igp[os] = sigp;
+        }
+        if (pa.sel_w[os] != wm) {
+          pa.sel_w[os] = wm;
+        }
+        if (pa.sel_best[os] != sbest) {
+          pa.sel_best[os] = sbest;
+        }
+      }
     }
     if (om != nm) {
       a.metric_out[o] = nm;
@@ -6815,14 +6946,6 @@ __global__ __launch_bounds__(256) void spf_route_patch_kernel(RoutePatchArgs pa)
 // lists and pair tables are per-lane reads of small read-only arrays (cache
 // resident across rows); only the row's source is wave-uniform and comes
 // through the constant path.  Distance gathers stay inside the row.
-enum : uint32_t {
-  kCmpWinner = 0, // MetricVectorUtils::CompareResult, in its order
-  kCmpTieWinner = 1,
-  kCmpTie = 2,
-  kCmpTieLooser = 3,
-  kCmpLooser = 4,
-  kCmpError = 5
-};
 struct RouteSelectArgs {
   const uint32_t* src;
   const uint32_t* dist; // query rows, stride Vp
@@ -15003,6 +15126,8 @@ struct spf_route_table {
   // (grow-only); evp0 .. evp1 time the patch kernel
   std::vector<uint32_t> h_ann_off, h_ann;
   std::vector<uint8_t> h_cflags;
+  std::vector<uint64_t> h_pair_off; // (selected columns: the pair tables too)
+  std::vector<uint16_t> h_pair;
   DevBuf<uint32_t> d_pt_rows, d_pt_cols, d_pt_doff, d_pt_dann, d_pt_lmet;
   DevBuf<uint64_t> d_pt_links;
   uint32_t pt_wave = 0;
@@ -15202,6 +15327,10 @@ int spf_route_table_create_sel(
   t->sel_of = sel_of;
   const uint32_t na = ann_offsets[num_prefixes];
   t->h_cflags.assign(sel->cand_flags, sel->cand_flags + na);
+  t->h_pair_off.assign(sel->pair_offsets, sel->pair_offsets + S + 1);
+  if (npair) {
+    t->h_pair.assign(sel->pair_codes, sel->pair_codes + npair);
+  }
   const size_t cells = (size_t)q->nq * S;
   int st = SPF_OK;
   if ((st = t->d_sel_col.upload(sel->columns, (size_t)S)) ||
@@ -15778,9 +15907,11 @@ int spf_route_table_changed_gone(spf_route_table* t, uint32_t i, uint64_t* bits)
   return SPF_OK;
 }
 
-int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
-                                  uint32_t* changed) {
-  SPF_ABI_RANGE("spf_route_table_patch_columns");
+// spf_route_table_patch_columns (sel_call false: a selected column is
+// SPF_E_UNSUPPORTED, SPF_MAP_NONE in a dirty list SPF_E_INVALID) and
+// spf_route_table_patch_columns_sel.
+static int route_patch_apply(spf_route_table* t, const spf_route_patch* p,
+                             const spf_route_select_desc* sel, uint32_t* changed, bool sel_call) {
   if (!t || !p) {
     return fail(SPF_E_INVALID, "null argument");
   }
@@ -15790,8 +15921,14 @@ int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
   spf_query* q = t->q;
   spf_graph* g = q->g;
   const uint32_t k = p->num_columns, P = t->P, nq = q->nq, pw = (P + 63) / 64;
+  const uint32_t nsel = sel_call && sel ? sel->num_selected : 0;
   // every check before anything is modified
   uint32_t na = 0, nd = 0;
+  std::vector<uint32_t> at(P, kInf32);    // column -> index into the patch
+  std::vector<uint32_t> sel_at(k, kInf32); // index into the patch -> index into sel
+  std::vector<uint8_t> special(k, 0);      // a column of the <.., true> instances
+  uint32_t nspecial = 0;
+  bool any_sel = false;
   if (k) {
     if (!p->columns || !p->ann_offsets) {
       return fail(SPF_E_INVALID, "null columns / ann_offsets");
@@ -15818,36 +15955,91 @@ int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
       }
     }
     for (uint32_t i = 0; i < nd; ++i) {
-      if (p->dirty_ann[i] >= g->V) { // SPF_MAP_NONE included: best is part of every patched cell
+      // (the old call: SPF_MAP_NONE included, best is part of every cell it patches)
+      if (p->dirty_ann[i] >= g->V && !(sel_call && p->dirty_ann[i] == SPF_MAP_NONE)) {
         return fail(SPF_E_INVALID, "dirty announcer out of range");
       }
     }
-    std::vector<uint8_t> seen(P, 0);
     for (uint32_t i = 0; i < k; ++i) {
       const uint32_t c = p->columns[i];
-      if (c >= P || seen[c]) {
+      if (c >= P || at[c] != kInf32) {
         return fail(SPF_E_INVALID, "column out of range or listed twice");
       }
-      seen[c] = 1;
+      at[c] = i;
     }
     for (uint32_t i = 0; i < k; ++i) {
       if (is_selected(t, p->columns[i])) {
-        return fail(SPF_E_UNSUPPORTED, "a selected column cannot be patched (its pair tables "
-                                       "would have to be replaced: rebuild the table)");
+        if (!sel_call) {
+          return fail(SPF_E_UNSUPPORTED, "a selected column cannot be patched (its pair tables "
+                                         "would have to be replaced: rebuild the table)");
+        }
+        any_sel = true;
+        special[i] = 1;
       }
+      for (uint32_t j = p->dirty_off ? p->dirty_off[i] : 0, e = p->dirty_off ? p->dirty_off[i + 1] : 0;
+           j < e; ++j) {
+        if (p->dirty_ann[j] == SPF_MAP_NONE) {
+          if (is_selected(t, p->columns[i])) {
+            return fail(SPF_E_INVALID, "SPF_MAP_NONE in the dirty list of a selected column");
+          }
+          special[i] = 1;
+        }
+      }
+      nspecial += special[i];
+    }
+  }
+  if (nsel) {
+    if (!sel->columns || !sel->pair_offsets) {
+      return fail(SPF_E_INVALID, "null selection array");
+    }
+    if (sel->pair_offsets[0] != 0) {
+      return fail(SPF_E_INVALID, "pair_offsets[0] != 0");
+    }
+    for (uint32_t j = 0; j < nsel; ++j) {
+      const uint32_t c = sel->columns[j];
+      if (c >= P || at[c] == kInf32) {
+        return fail(SPF_E_INVALID, "a selection column that the patch does not list");
+      }
+      if (!is_selected(t, c)) {
+        return fail(SPF_E_INVALID, "a selection column that is not a selected column of the table");
+      }
+      if (sel_at[at[c]] != kInf32) {
+        return fail(SPF_E_INVALID, "selection column listed twice");
+      }
+      sel_at[at[c]] = j;
+      const uint64_t n = p->ann_offsets[at[c] + 1] - p->ann_offsets[at[c]];
+      if (n > 32) {
+        return fail(SPF_E_INVALID, "a selected column has more than 32 candidates");
+      }
+      if (sel->pair_offsets[j + 1] < sel->pair_offsets[j] ||
+          sel->pair_offsets[j + 1] - sel->pair_offsets[j] < n * (n - (n ? 1 : 0)) / 2) {
+        return fail(SPF_E_INVALID, "pair table shorter than n(n-1)/2");
+      }
+      if (n && !sel->cand_flags) {
+        return fail(SPF_E_INVALID, "null cand_flags");
+      }
+    }
+    if (sel->pair_offsets[nsel] && !sel->pair_codes) {
+      return fail(SPF_E_INVALID, "null pair_codes");
+    }
+  }
+  for (uint32_t i = 0; i < k; ++i) {
+    if (is_selected(t, p->columns[i]) && sel_at[i] == kInf32) {
+      return fail(SPF_E_INVALID, "a listed selected column without its pair table");
     }
   }
   HIP_TRY(hipSetDevice(g->device));
-  // the patched announcer arrays, assembled beside the resident ones
+  // the patched announcer arrays (and, with a selected column listed, the pair
+  // tables), assembled beside the resident ones
   std::vector<uint32_t> off, ann;
   std::vector<uint8_t> cflags;
+  std::vector<uint64_t> pair_off;
+  std::vector<uint16_t> pair;
   DevBuf<uint32_t> d_off, d_ann;
   DevBuf<uint8_t> d_cflags;
+  DevBuf<uint64_t> d_pair_off;
+  DevBuf<uint16_t> d_pair;
   if (k) {
-    std::vector<uint32_t> at(P, kInf32); // column -> index into the patch
-    for (uint32_t i = 0; i < k; ++i) {
-      at[p->columns[i]] = i;
-    }
     off.assign((size_t)P + 1, 0);
     ann.reserve(t->h_ann.size() + na);
     for (uint32_t c = 0; c < P; ++c) {
@@ -15864,6 +16056,8 @@ int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
         cflags.resize(at0 + n, 0);
         if (i == kInf32 && n) {
           std::copy_n(t->h_cflags.begin() + t->h_ann_off[c], n, cflags.begin() + at0);
+        } else if (n && sel_at[i] != kInf32) {
+          std::copy_n(sel->cand_flags + p->ann_offsets[i], n, cflags.begin() + at0);
         }
       }
       if (n) {
@@ -15872,14 +16066,56 @@ int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
       off[c + 1] = (uint32_t)ann.size();
     }
     int st = SPF_OK;
+    if (any_sel) {
+      pair_off.assign((size_t)t->S + 1, 0);
+      pair.reserve(t->h_pair.size());
+      for (uint32_t s0 = 0; s0 < t->S; ++s0) {
+        const uint32_t i = at[t->sel_col[s0]];
+        if (i != kInf32) {
+          const uint32_t j = sel_at[i];
+          pair.insert(pair.end(), sel->pair_codes + sel->pair_offsets[j],
+                      sel->pair_codes + sel->pair_offsets[j + 1]);
+        } else {
+          pair.insert(pair.end(), t->h_pair.begin() + t->h_pair_off[s0],
+                      t->h_pair.begin() + t->h_pair_off[s0 + 1]);
+        }
+        pair_off[s0 + 1] = pair.size();
+      }
+      if ((st = d_pair_off.upload(pair_off.data(), pair_off.size())) ||
+          (st = d_pair.upload(pair.data(), pair.size()))) {
+        return st;
+      }
+    }
     if ((st = d_off.upload(off.data(), off.size())) || (st = d_ann.upload(ann.data(), ann.size())) ||
         (st = d_cflags.upload(cflags.data(), cflags.size()))) {
       return st;
     }
     if (nq) {
-      if ((st = t->d_pt_cols.upload(p->columns, k)) ||
-          (st = t->d_pt_doff.upload(p->dirty_off, p->dirty_off ? (size_t)k + 1 : 0)) ||
-          (st = t->d_pt_dann.upload(p->dirty_ann, nd))) {
+      // the listed columns by kernel instance: the plain ones first, then
+      // those of the <.., true> instances; the dirty lists in that order
+      std::vector<uint32_t> cols(p->columns, p->columns + k), doff, dann;
+      if (nspecial) {
+        cols.clear();
+        doff.assign(1, 0);
+        for (uint32_t pass = 0; pass < 2; ++pass) {
+          for (uint32_t i = 0; i < k; ++i) {
+            if (special[i] != pass) {
+              continue;
+            }
+            cols.push_back(p->columns[i]);
+            if (p->dirty_off) {
+              dann.insert(dann.end(), p->dirty_ann + p->dirty_off[i],
+                          p->dirty_ann + p->dirty_off[i + 1]);
+              doff.push_back((uint32_t)dann.size());
+            }
+          }
+        }
+      }
+      const bool moved = nspecial && p->dirty_off;
+      if ((st = t->d_pt_cols.upload(cols.data(), k)) ||
+          (st = t->d_pt_doff.upload(moved ? doff.data() : p->dirty_off,
+                                    p->dirty_off ? (size_t)k + 1 : 0)) ||
+          (st = t->d_pt_dann.upload(moved ? dann.data() : p->dirty_ann, nd))) {
         return st;
       }
       if (t->d_pt_links.reserve((size_t)(t->lk_off.back() / P * k)) != hipSuccess ||
@@ -15920,13 +16156,19 @@ int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
   // before they are released
   HIP_TRY(hipStreamSynchronize(g->stream));
   if (k) {
-    t->d_ann_off = std::move(d_off); // (the old arrays go with d_off / d_ann / d_cflags)
+    t->d_ann_off = std::move(d_off); // (the old arrays go with d_off / d_ann / d_cflags / d_pair*)
     t->d_ann = std::move(d_ann);
     t->h_ann_off = std::move(off);
     t->h_ann = std::move(ann);
     if (t->S) {
       t->d_cflags = std::move(d_cflags);
       t->h_cflags = std::move(cflags);
+    }
+    if (any_sel) {
+      t->d_pair_off = std::move(d_pair_off);
+      t->d_pair = std::move(d_pair);
+      t->h_pair_off = std::move(pair_off);
+      t->h_pair = std::move(pair);
     }
   }
   ++t->epoch;
@@ -15944,7 +16186,7 @@ int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
   }
   HIP_TRY(hipEventRecord(t->evp0, g->stream));
   if (k) {
-    RoutePatchArgs a{};
+    RoutePatchSelArgs a{};
     a.t.row = g->d_row;
     a.t.col = g->d_col;
     a.t.wout = g->d_wout;
@@ -15969,31 +16211,60 @@ int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
     a.t.Vp = q->Vp;
     a.t.P = P;
     a.t.nq = nq;
-    a.cols = t->d_pt_cols;
-    a.dirty_off = p->dirty_off ? t->d_pt_doff.p : nullptr;
+    a.t.sel_of = t->d_sel_of; // (null without selected columns; the <.., true> instances only)
+    a.t.S = t->S;
+    a.pair_off = t->d_pair_off;
+    a.pair = t->d_pair;
+    a.cflags = t->d_cflags;
+    a.sel_w = t->d_sel_w;
+    a.sel_best = t->d_sel_best;
+    a.sel_igp = t->d_sel_igp;
     a.dirty_ann = t->d_pt_dann;
-    a.s_links = t->d_pt_links;
-    a.s_lmet = t->d_pt_lmet;
     a.bits = t->d_diff;
     a.count = t->d_count;
-    a.k = k;
     a.pw = pw;
     a.routes_only = t->diff_routes ? 1u : 0u;
-    // long lists: 256 lanes per row; else a wave per row where its LDS slice holds the row's links
-    const uint32_t nwave = k > 256 ? 0 : t->pt_wave;
-    if (nwave) {
-      a.rows = t->d_pt_rows;
-      a.nrows = nwave;
-      SPF_LAUNCH_AS("spf_route_patch_kernel", spf_route_patch_kernel<4>, dim3((nwave + 3) / 4),
-                    dim3(256), 0, g->stream, a);
-      HIP_TRY(hipGetLastError());
-    }
-    if (nwave < nq) {
-      a.rows = t->d_pt_rows + nwave;
-      a.nrows = nq - nwave;
-      SPF_LAUNCH_AS("spf_route_patch_kernel", spf_route_patch_kernel<1>, dim3(nq - nwave),
-                    dim3(256), 0, g->stream, a);
-      HIP_TRY(hipGetLastError());
+    // the plain columns [0, k - nspecial) through the instances as they were,
+    // the others through the <.., true> ones; each part has its own scratch cells
+    for (uint32_t part = 0; part < 2; ++part) {
+      const uint32_t c0 = part ? k - nspecial : 0, kp = part ? nspecial : k - nspecial;
+      if (!kp) {
+        continue;
+      }
+      a.cols = t->d_pt_cols + c0;
+      a.dirty_off = p->dirty_off ? t->d_pt_doff.p + c0 : nullptr;
+      a.s_links = t->d_pt_links + (size_t)(t->lk_off.back() / P * c0);
+      a.s_lmet = t->d_pt_lmet + (size_t)(t->lm_off.back() / P * c0);
+      a.k = kp;
+      // long lists: 256 lanes per row; else a wave per row where its LDS slice holds the row's links
+      const uint32_t nwave = kp > 256 ? 0 : t->pt_wave;
+      if (nwave) {
+        a.rows = t->d_pt_rows;
+        a.nrows = nwave;
+        if (part) {
+          auto* kern = spf_route_patch_kernel<4, true>;
+          SPF_LAUNCH_AS("spf_route_patch_kernel", kern, dim3((nwave + 3) / 4), dim3(256), 0,
+                        g->stream, a);
+        } else {
+          SPF_LAUNCH_AS("spf_route_patch_kernel", spf_route_patch_kernel<4>,
+                        dim3((nwave + 3) / 4), dim3(256), 0, g->stream,
+                        static_cast<const RoutePatchArgs&>(a));
+        }
+        HIP_TRY(hipGetLastError());
+      }
+      if (nwave < nq) {
+        a.rows = t->d_pt_rows + nwave;
+        a.nrows = nq - nwave;
+        if (part) {
+          auto* kern = spf_route_patch_kernel<1, true>;
+          SPF_LAUNCH_AS("spf_route_patch_kernel", kern, dim3(nq - nwave), dim3(256), 0, g->stream,
+                        a);
+        } else {
+          SPF_LAUNCH_AS("spf_route_patch_kernel", spf_route_patch_kernel<1>, dim3(nq - nwave),
+                        dim3(256), 0, g->stream, static_cast<const RoutePatchArgs&>(a));
+        }
+        HIP_TRY(hipGetLastError());
+      }
     }
   }
   HIP_TRY(hipEventRecord(t->evp1, g->stream));
@@ -16002,6 +16273,18 @@ int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
   }
   HIP_TRY(hipStreamSynchronize(g->stream));
   return SPF_OK;
+}
+
+int spf_route_table_patch_columns(spf_route_table* t, const spf_route_patch* p,
+                                  uint32_t* changed) {
+  SPF_ABI_RANGE("spf_route_table_patch_columns");
+  return route_patch_apply(t, p, nullptr, changed, false);
+}
+
+int spf_route_table_patch_columns_sel(spf_route_table* t, const spf_route_patch* p,
+                                      const spf_route_select_desc* sel, uint32_t* changed) {
+  SPF_ABI_RANGE("spf_route_table_patch_columns_sel");
+  return route_patch_apply(t, p, sel, changed, true);
 }
 
 int spf_route_table_patch_elapsed_ms(spf_route_table* t, float* ms) {
