@@ -503,3 +503,49 @@ def test_same_node_rebuilds_reuse_query(mods, net):
         os.environ.pop("OPENR_LS_QUERY_CACHE", None)
     if net == "grid":
         assert E.get_counters().get("decision.spf_query_reuses", 0) > 0
+
+
+@pytest.mark.parametrize("cache", [None, "0"], ids=["cache", "nocache"])
+def test_hop_bound_flips_under_live_query(mods, cache, monkeypatch):
+    """A 10-node star whose metric (2^32 / 7) fits 32-bit rows only under the
+    transit hop bound (tests/test_abi_gpu.py::test_hop_bound_follows_drains):
+    draining node 8 cuts node 9 off the hub and withdraws the bound, undraining
+    restores it, so the graph flips between the 32-bit plans and the 64-bit
+    plan while Engine::lastQuery is alive (its reuse key is only sources and
+    flags).  Each step asks first for the SpfResult the step before asked for
+    last, so the same sources meet the cached query across the flip.  After
+    every step every node's metric and hop-count SpfResult equals the
+    oracle's, with the query cache on and off."""
+    if cache is None:
+        monkeypatch.delenv("OPENR_LS_QUERY_CACHE", raising=False)
+    else:
+        monkeypatch.setenv("OPENR_LS_QUERY_CACHE", cache)
+    E, O = mods
+    w = (1 << 32) // 7
+    names = [f"s{i}" for i in range(10)]
+    adjs = {n: [] for n in names}
+    for k, (u, v) in enumerate([(0, x) for x in range(1, 9)] + [(8, 9)]):
+        a, b = names[u], names[v]
+        adjs[a].append(T.createAdjacency(b, f"if_{a}_{b}", f"if_{b}_{a}", f"fe80::{k + 1:x}:1",
+                                         f"10.0.{k}.1", w, 50000 + k))
+        adjs[b].append(T.createAdjacency(a, f"if_{b}_{a}", f"if_{a}_{b}", f"fe80::{k + 1:x}:2",
+                                         f"10.0.{k}.2", w, 51000 + k))
+    for n in names:
+        for adj in adjs[n]:
+            adj.rtt = 100  # (createAdjacency's metric * 100 does not fit the i32 field)
+    dbs = [T.createAdjDb(n, adjs[n], 101 + i, False, "0") for i, n in enumerate(names)]
+    ea, _ = RZ.load(E, {"0": dbs}, [], 0)
+    oa, _ = RZ.load(O, {"0": dbs}, [], 0)
+    db8 = copy.deepcopy(dbs[8])
+    for step in range(7):
+        passes = [(True, names), (False, names)]
+        if step % 2:
+            passes = [(False, names[::-1]), (True, names[::-1])]
+        for use_metric, order in passes:
+            for node in order:
+                _spf_equal(ea["0"], oa["0"], node, use_metric)
+        db8.isOverloaded = not db8.isOverloaded
+        assert ea["0"].updateAdjacencyDatabase(db8) == oa["0"].updateAdjacencyDatabase(db8)
+    for node in names:
+        _spf_equal(ea["0"], oa["0"], node, True)
+        _spf_equal(ea["0"], oa["0"], node, False)
