@@ -649,6 +649,61 @@ int spf_route_table_patch_columns_sel(
  * (clearing the bitmap and spf_route_patch_kernel). */
 int spf_route_table_patch_elapsed_ms(spf_route_table* t, float* ms);
 
+/* A topology change that keeps the CSR layout (metrics patched with
+ * spf_graph_patch_metrics, transit bits with spf_graph_set_transit), in place:
+ * `q` is an all-rows query over the SAME graph as the table's, with the same
+ * sources in the same order, SPF_F_NEXTHOPS, no unit metric, no ignore lists,
+ * 32-bit rows, and it has run since the graph changed.  It may be the table's
+ * own query re-run, or a new one (the planner fixes a query's plan at creation,
+ * so a metric change that ends or starts a uniform metric needs a new one).
+ * spf_route_refresh_kernel recomputes every cell of the listed rows from q's
+ * rows and masks and compares each with the cell it replaces in the same pass.
+ * After the call every cell of a listed row is bit-equal to the cell of a table
+ * freshly created over `q` with the table's announcer lists and flags, and run
+ * (metric, best, link words and, SPF_RT_LFA, link metrics).  Rows not listed
+ * are neither read nor written: the caller vouches that their SPF rows, masks,
+ * own link metrics and (SPF_RT_LFA) neighbours' rows are as before; the call
+ * does not check it.
+ * The changed bitmap of `t` becomes what spf_route_table_diff(before, after)
+ * reports for the listed rows (spf_route_table_diff_routes is honoured);
+ * unlisted rows are clear; changed[i] (NULL: not wanted) = the popcount of row
+ * i.  `t` is left as after an equal-layout diff: the epoch moved (an earlier
+ * pack is stale), spf_route_table_changed, _delta_pack, _delta_fetch and
+ * _fetch_cells work, _changed_gone reports no gone columns, a later
+ * _patch_columns or _refresh_rows replaces the bitmap, and a later
+ * spf_route_table_run reproduces the same cells from `q`.
+ * The table is bound to `q` from then on and the user counts of the lifetime
+ * rule move with it: the old query can be destroyed, `q` cannot while `t`
+ * lives (SPF_E_INVALID).
+ * Everything is checked on the host first; on an error the table, its bitmap,
+ * its pack state and its query binding are as before the call.
+ * SPF_E_INVALID: a null `t` or `q`, a table or a `q` that has not run, a `q`
+ * over another graph, with other sources, without next hops, with unit metric
+ * or ignore lists, a row >= the table's rows or listed twice.
+ * SPF_E_UNSUPPORTED: 64-bit rows; a table with selected columns (BGP columns:
+ * their selection words follow the rows too).  num_rows == 0 with a non-null
+ * `rows` is SPF_OK: the bitmap is all clear and the binding moves.
+ * Memory: the cells the call replaces are kept in a previous-cell store of the
+ * listed rows' size (grow-only; with every row listed one more cell store).
+ * No second graph, no second rows or masks and no host maps are needed. */
+int spf_route_table_refresh_rows(
+    spf_route_table* t, spf_query* q,
+    uint32_t num_rows, const uint32_t* rows /* distinct, < nq; NULL: every row */,
+    uint32_t* changed /*[rows of t] or NULL*/);
+/* Device time of the last spf_route_table_refresh_rows (clearing the bitmap
+ * and spf_route_refresh_kernel). */
+int spf_route_table_refresh_elapsed_ms(spf_route_table* t, float* ms);
+/* The cells as they were before the last refresh: spf_route_table_fetch_cells'
+ * arguments and packing; any (row, column), listed in that refresh or not (a
+ * listed row's cells come from the store, the others are the resident ones).
+ * What getRouteDelta's MPLS side needs without an older table: the entry of a
+ * label before the change, from cells of label columns that may not have
+ * changed.  Answers until the next run, patch or refresh of `t`;
+ * SPF_E_INVALID when no refresh is current. */
+int spf_route_table_fetch_cells_prev(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols,
+    uint32_t* metric, uint32_t* best, uint64_t* links, uint32_t* link_metrics);
+
 /* The delta itself (getRouteDelta, Decision.cpp:47-85: the updates and
  * deletes, not their number) of every node as one record list built on the
  * device: the changed cells of the last diff, compacted out of the bitmaps,

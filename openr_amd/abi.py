@@ -105,6 +105,9 @@ EXPORTED_SYMBOLS = (
     "spf_route_table_patch_columns",
     "spf_route_table_patch_columns_sel",
     "spf_route_table_patch_elapsed_ms",
+    "spf_route_table_refresh_rows",
+    "spf_route_table_refresh_elapsed_ms",
+    "spf_route_table_fetch_cells_prev",
     "spf_cluster_unique_id",
     "spf_cluster_create_local",
     "spf_cluster_create_rank",
@@ -496,6 +499,10 @@ def load():
                                                         C.POINTER(_RouteSelectDesc), pu32]),
         "spf_route_table_patch_elapsed_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "spf_route_table_fetch_cells_igp": (C.c_int, [vp, C.c_uint64, pu32, pu32, pu32]),
+        "spf_route_table_refresh_rows": (C.c_int, [vp, vp, u32, pu32, pu32]),
+        "spf_route_table_refresh_elapsed_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+        "spf_route_table_fetch_cells_prev": (C.c_int, [vp, C.c_uint64, pu32, pu32, pu32, pu32,
+                                                       pu64, pu32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
@@ -1177,7 +1184,7 @@ class RouteTable:
             "link_metrics": lmet[: z.link_metrics], "gone_off": gone_off, "gone": gone[: z.gone],
         }
 
-    def fetch_cells(self, rows, cols, degs=None):
+    def fetch_cells(self, rows, cols, degs=None, _fn="spf_route_table_fetch_cells"):
         """spf_route_table_fetch_cells: (metric [n], best [n], links, link
         metrics) of the cells (rows[k], cols[k]); links are packed in list
         order, link_words(rows[k]) words each, link metrics (SPF_RT_LFA, needs
@@ -1193,11 +1200,42 @@ class RouteTable:
         best = np.zeros(max(n, 1), dtype=np.uint32)
         links = np.zeros(max(nl, 1), dtype=np.uint64)
         lmet = np.zeros(max(nm, 1), dtype=np.uint32)
-        _check(load().spf_route_table_fetch_cells(
+        _check(getattr(load(), _fn)(
             self.h, n, _p(rows, C.c_uint32) if n else None, _p(cols, C.c_uint32) if n else None,
             _p(metric, C.c_uint32), _p(best, C.c_uint32), _p(links, C.c_uint64),
-            _p(lmet, C.c_uint32) if self.lfa else None), "spf_route_table_fetch_cells")
+            _p(lmet, C.c_uint32) if self.lfa else None), _fn)
         return metric[:n], best[:n], links[:nl], lmet[:nm]
+
+    def fetch_cells_prev(self, rows, cols, degs=None):
+        """spf_route_table_fetch_cells_prev: fetch_cells of the cells as they
+        were before the last refresh_rows (any row, listed there or not)."""
+        return self.fetch_cells(rows, cols, degs, _fn="spf_route_table_fetch_cells_prev")
+
+    def refresh_rows(self, query: "Query", rows=None) -> np.ndarray:
+        """spf_route_table_refresh_rows: the listed rows (None: every row) are
+        recomputed in place from `query` (the table's own re-run, or a new one
+        over the same graph and sources), to which the table is bound from
+        then on; returns the changed columns per row.  The table is left as
+        after an equal-layout diff (changed, delta_pack, fetch_cells) and
+        fetch_cells_prev reads the cells it replaced."""
+        out = np.zeros(max(self.n, 1), dtype=np.uint32)
+        if rows is None:
+            n, ptr = 0, None
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.uint32)
+            n = len(rows)
+            ptr = _p(rows if n else np.zeros(1, dtype=np.uint32), C.c_uint32)
+        _check(load().spf_route_table_refresh_rows(self.h, query.h, n, ptr, _p(out, C.c_uint32)),
+               "spf_route_table_refresh_rows")
+        self.num_gone = 0
+        return out[: self.n]
+
+    def refresh_ms(self) -> float:
+        """Device time of the last refresh_rows."""
+        ms = C.c_float()
+        _check(load().spf_route_table_refresh_elapsed_ms(self.h, C.byref(ms)),
+               "spf_route_table_refresh_elapsed_ms")
+        return float(ms.value)
 
     def patch_columns(self, columns, announcers, dirty=None) -> np.ndarray:
         """spf_route_table_patch_columns: column columns[k] gets the announcer

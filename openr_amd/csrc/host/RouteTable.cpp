@@ -418,6 +418,11 @@ AllNodesRouteTable::AllNodesRouteTable(
   ids_ = eng.ids;
   overloaded_.assign(eng.overloaded.begin(), eng.overloaded.end());
   row_ = eng.row;
+  col_ = eng.col;
+  rev_ = eng.rev;
+  linkId_ = eng.linkId;
+  metric_ = eng.metric;
+  numLinks_ = (uint32_t)eng.links.size();
   halfLink_.resize(eng.col.size());
   for (size_t e = 0; e < eng.col.size(); ++e) {
     halfLink_[e] = eng.links[eng.linkId[e]];
@@ -681,10 +686,15 @@ std::optional<RibMplsEntry> AllNodesRouteTable::nodeLabelEntry(
 
 std::optional<RibMplsEntry> AllNodesRouteTable::mplsEntry(
     uint32_t i, const Row& r, int32_t label) const {
+  return mplsEntryWith(i, r, label, adjLabels_[i]);
+}
+
+std::optional<RibMplsEntry> AllNodesRouteTable::mplsEntryWith(
+    uint32_t i, const Row& r, int32_t label, const std::vector<AdjLabel>& adj) const {
   if (auto e = nodeLabelEntry(i, r, label)) {
     return e;
   }
-  for (const AdjLabel& a : adjLabels_[i]) {
+  for (const AdjLabel& a : adj) {
     if (a.label == label) {
       return RibMplsEntry(
           label,
@@ -794,6 +804,7 @@ std::vector<uint32_t> AllNodesRouteTable::diff(const AllNodesRouteTable& older) 
   }
   older_ = &older;
   patchDelta_ = false;
+  topoDelta_ = false;
   return changed;
 }
 
@@ -1042,6 +1053,7 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
   goneNew_ = std::move(goneNew);
   older_ = &older;
   patchDelta_ = false;
+  topoDelta_ = false;
   return changed;
 }
 
@@ -1471,6 +1483,7 @@ std::vector<uint32_t> AllNodesRouteTable::applyPrefixChanges(
   diffed_ = true;
   mapped_ = false;
   patchDelta_ = true;
+  topoDelta_ = false;
   older_ = nullptr;
   goneCols_.clear();
   goneNew_.clear();
@@ -1479,6 +1492,265 @@ std::vector<uint32_t> AllNodesRouteTable::applyPrefixChanges(
     rowOf_[i] = i;
   }
   Counters::add("decision.route_table_patch_us", usSince(tp));
+  return counts;
+}
+
+std::vector<uint32_t> routeRefreshRowList(
+    const std::vector<uint8_t>& affected, const std::vector<uint32_t>& row,
+    const std::vector<uint32_t>& col, const std::vector<uint32_t>& changedTails, bool lfa) {
+  const size_t V = affected.size();
+  if (row.size() != V + 1 || (V && row[V] > col.size())) {
+    throw std::invalid_argument("routeRefreshRowList: the CSR does not match the nodes");
+  }
+  std::vector<uint8_t> listed(affected.begin(), affected.end());
+  if (lfa) {
+    for (size_t i = 0; i < V; ++i) {
+      for (uint32_t e = row[i]; e < row[i + 1] && !listed[i]; ++e) {
+        listed[i] = col[e] < V && affected[col[e]];
+      }
+    }
+    for (const uint32_t t : changedTails) {
+      listed.at(t) = 1;
+    }
+  }
+  std::vector<uint32_t> out;
+  for (size_t i = 0; i < V; ++i) {
+    if (listed[i]) {
+      out.push_back((uint32_t)i);
+    }
+  }
+  return out;
+}
+
+AllNodesRouteTable::Row AllNodesRouteTable::fetchPrevRow(uint32_t i) const {
+  Row r;
+  const size_t P = numCols();
+  r.deg = row_[i + 1] - row_[i];
+  r.W = (r.deg + 63) / 64;
+  r.metric.resize(P);
+  r.best.resize(P);
+  r.links.resize(std::max<size_t>(1, P * r.W));
+  if (lfa_) {
+    r.lmet.resize(std::max<size_t>(1, P * r.deg));
+  }
+  std::vector<uint32_t> rows(P, i), cols(P);
+  for (size_t p = 0; p < P; ++p) {
+    cols[p] = (uint32_t)p;
+  }
+  if (int s = spf_route_table_fetch_cells_prev(
+          table_.get(), P, rows.data(), cols.data(), r.metric.data(), r.best.data(),
+          r.links.data(), lfa_ ? r.lmet.data() : nullptr);
+      s != SPF_OK) {
+    tableFailure("spf_route_table_fetch_cells_prev", s);
+  }
+  return r;
+}
+
+std::vector<uint32_t> AllNodesRouteTable::applyTopologyChanges(const LinkState& ls) {
+  const auto tp = std::chrono::steady_clock::now();
+  // ---- every refusal, before anything is touched
+  if (hasBorder_ || bgpColumns_) {
+    throw std::invalid_argument(
+        "AllNodesRouteTable::applyTopologyChanges: a table built with borderNodes or bgpColumns");
+  }
+  if (ls.getArea() != area_) {
+    throw std::invalid_argument("AllNodesRouteTable::applyTopologyChanges: another area");
+  }
+  LinkState::Engine& eng = ls.engine();
+  if (eng.exact) {
+    throw std::invalid_argument(
+        "AllNodesRouteTable::applyTopologyChanges: metric 0 / 64-bit sums need the exact kernel");
+  }
+  if (eng.names != names_ || eng.row != row_ || eng.col != col_ || eng.rev != rev_ ||
+      eng.linkId != linkId_) {
+    throw std::invalid_argument(
+        "AllNodesRouteTable::applyTopologyChanges: nodes or links changed (build a fresh table)");
+  }
+  const uint32_t V = (uint32_t)names_.size();
+  const size_t E = col_.size();
+  // (a LinkState updated in place keeps its Link objects: the usual case is
+  // pointer equality, and only other objects are compared and taken over)
+  std::vector<std::pair<uint32_t, std::shared_ptr<Link>>> moved;
+  for (uint32_t i = 0; i < V; ++i) {
+    for (uint32_t e = row_[i]; e < row_[i + 1]; ++e) {
+      const std::shared_ptr<Link>& now = eng.links[eng.linkId[e]];
+      if (now == halfLink_[e]) {
+        continue;
+      }
+      moved.emplace_back(e, now);
+      const Link& a = *halfLink_[e];
+      const Link& b = *now;
+      const std::string& node = names_[i];
+      if (!(a == b && a.getArea() == b.getArea() &&
+            a.getIfaceFromNode(node) == b.getIfaceFromNode(node) &&
+            a.getNhV4FromNode(node) == b.getNhV4FromNode(node) &&
+            a.getNhV6FromNode(node) == b.getNhV6FromNode(node))) {
+        throw std::invalid_argument(
+            "AllNodesRouteTable::applyTopologyChanges: a link changed its identity");
+      }
+    }
+  }
+  {
+    std::vector<int32_t> nodeLabel(V, 0);
+    for (const auto& [node, db] : ls.getAdjacencyDatabases()) {
+      if (db.nodeLabel == 0 || !isMplsLabelValid(db.nodeLabel)) {
+        continue;
+      }
+      if (auto it = ids_.find(node); it != ids_.end()) {
+        nodeLabel[it->second] = db.nodeLabel;
+      }
+    }
+    if (nodeLabel != nodeLabel_) {
+      throw std::invalid_argument(
+          "AllNodesRouteTable::applyTopologyChanges: a node label changed (build a fresh table)");
+    }
+  }
+  // ---- edge deltas between the two CSR snapshots, changed half-edges
+  auto desc = [&](const std::vector<uint64_t>& metric, const std::vector<uint8_t>& ov) {
+    spf_graph_desc d{};
+    d.num_nodes = V;
+    d.num_edges = (uint32_t)E;
+    d.row_ptr = row_.data();
+    d.col = col_.data();
+    d.metric = metric.data();
+    d.link_id = linkId_.data();
+    d.rev = rev_.data();
+    d.node_overloaded = ov.data();
+    d.num_links = numLinks_;
+    d.device = getSpfDevice();
+    return d;
+  };
+  const std::vector<uint8_t> ovNew(eng.overloaded.begin(), eng.overloaded.end());
+  std::vector<uint32_t> edges, tails;
+  std::vector<uint64_t> metrics;
+  for (uint32_t i = 0; i < V; ++i) {
+    for (uint32_t e = row_[i]; e < row_[i + 1]; ++e) {
+      if (metric_[e] != eng.metric[e]) {
+        edges.push_back(e);
+        metrics.push_back(eng.metric[e]);
+        if (tails.empty() || tails.back() != i) {
+          tails.push_back(i);
+        }
+      }
+    }
+  }
+  const bool drained = ovNew != overloaded_;
+  // (the deltas only choose rows: not needed when every row is listed, none
+  // without a changed metric; a changed half-edge gives at most two)
+  uint32_t nd = 0;
+  std::vector<spf_edge_delta> deltas(drained ? 0 : 2 * edges.size());
+  if (!deltas.empty()) {
+    const spf_graph_desc da = desc(metric_, overloaded_), db = desc(eng.metric, ovNew);
+    if (int s = spf_graph_diff(&da, &db, deltas.data(), (uint32_t)deltas.size(), &nd);
+        s != SPF_OK || nd > deltas.size()) {
+      tableFailure("spf_graph_diff", s);
+    }
+  }
+  // ---- the rows: every row when an overload bit flipped, else the screen's
+  // on the resident rows (before the graph is patched), closed for LFA
+  std::vector<uint32_t> rows;
+  std::vector<uint32_t> src(V);
+  for (uint32_t i = 0; i < V; ++i) {
+    src[i] = i;
+  }
+  if (!drained && !edges.empty()) {
+    std::vector<uint8_t> affected(V, 0);
+    if (nd) {
+      void *dist = nullptr, *nh = nullptr;
+      uint32_t eb = 0;
+      uint64_t nhWords = 0;
+      if (int s = spf_query_device_rows(query_.get(), &dist, &eb, &nh, &nhWords);
+          s != SPF_OK || eb != 4) {
+        tableFailure("spf_query_device_rows", s);
+      }
+      if (int s = spf_table_screen(graph_.get(), (const uint32_t*)dist,
+                                   spf_query_row_stride(query_.get()), V, src.data(),
+                                   deltas.data(), nd, affected.data());
+          s != SPF_OK) {
+        tableFailure("spf_table_screen", s);
+      }
+    }
+    if (nd != 2 * edges.size()) {
+      // parallel links that exchanged metrics cancel out of the multiset
+      // deltas, yet which of them is tight is a link bit of their tail's cells
+      for (const uint32_t t : tails) {
+        affected[t] = 1;
+      }
+    }
+    rows = routeRefreshRowList(affected, row_, col_, tails, lfa_);
+  }
+  std::vector<uint32_t> counts(V, 0);
+  spf_query* q = query_.get();
+  std::unique_ptr<spf_query, QueryDeleter> fresh;
+  if (drained || !edges.empty()) {
+    // ---- from here on a failure leaves the table unusable
+    if (!edges.empty()) {
+      if (int s = spf_graph_patch_metrics(graph_.get(), (uint32_t)edges.size(), edges.data(),
+                                          metrics.data());
+          s != SPF_OK) {
+        tableFailure("spf_graph_patch_metrics", s);
+      }
+    }
+    if (drained) {
+      if (int s = spf_graph_set_transit(graph_.get(), ovNew.data()); s != SPF_OK) {
+        tableFailure("spf_graph_set_transit", s);
+      }
+    }
+    spf_query_desc qd{};
+    qd.num_queries = V;
+    qd.sources = src.data();
+    qd.flags = SPF_F_NEXTHOPS;
+    spf_query* nq = nullptr;
+    if (int s = spf_query_create(graph_.get(), &qd, &nq); s != SPF_OK) {
+      tableFailure("spf_query_create", s);
+    }
+    fresh.reset(nq);
+    if (int s = spf_query_run(nq); s != SPF_OK) {
+      tableFailure("spf_query_run", s);
+    }
+    q = nq;
+  }
+  // (nothing moved on the graph: an all-clear bitmap over the table's own query)
+  const uint32_t none = 0;
+  if (int s = spf_route_table_refresh_rows(
+          table_.get(), q, drained ? 0 : (uint32_t)rows.size(),
+          drained ? nullptr : rows.empty() ? &none : rows.data(), counts.data());
+      s != SPF_OK) {
+    tableFailure("spf_route_table_refresh_rows", s);
+  }
+  if (fresh) {
+    query_ = std::move(fresh); // (the old query goes: the table is bound to the new one)
+    if (int s = spf_query_elapsed_ms(query_.get(), &spfMs_); s != SPF_OK) {
+      tableFailure("elapsed", s);
+    }
+  } else {
+    spfMs_ = 0;
+  }
+  if (int s = spf_route_table_refresh_elapsed_ms(table_.get(), &refreshMs_); s != SPF_OK) {
+    tableFailure("spf_route_table_refresh_elapsed_ms", s);
+  }
+  refreshRows_ = drained ? V : rows.size();
+  // ---- the host's view: metrics, drain bits, links, adjacency labels
+  metric_ = eng.metric;
+  overloaded_ = ovNew;
+  for (auto& [e, link] : moved) {
+    halfLink_[e] = std::move(link);
+  }
+  prevAdjLabels_ = std::move(adjLabels_);
+  adjLabels_.clear();
+  collectAdjLabels(ls);
+  diffed_ = true;
+  mapped_ = false;
+  patchDelta_ = false;
+  topoDelta_ = true;
+  older_ = nullptr;
+  goneCols_.clear();
+  goneNew_.clear();
+  rowOf_.resize(V);
+  for (uint32_t i = 0; i < V; ++i) {
+    rowOf_[i] = i;
+  }
+  Counters::add("decision.route_table_refresh_us", usSince(tp));
   return counts;
 }
 
@@ -1527,11 +1799,25 @@ std::vector<int32_t> AllNodesRouteTable::labelCandidates(
   }
   const uint32_t ia = rowOf_[i];
   const bool hasOld = ia != SPF_MAP_NONE;
-  const size_t P = prefixes_.size(), Pa = older_->prefixes_.size();
+  const size_t P = prefixes_.size();
   std::set<int32_t> labels;
   for (const AdjLabel& a : adjLabels_[i]) {
     labels.insert(a.label);
   }
+  if (topoDelta_) {
+    // the older side is this table before the call: same label columns, the
+    // previous adjacency labels, nothing gone
+    for (const AdjLabel& a : prevAdjLabels_[i]) {
+      labels.insert(a.label);
+    }
+    for (size_t k = 0; k < n; ++k) {
+      if (!isUni(cols[k])) {
+        labels.insert(owners_[cols[k] - P].label);
+      }
+    }
+    return {labels.begin(), labels.end()};
+  }
+  const size_t Pa = older_->prefixes_.size();
   if (hasOld) {
     for (const AdjLabel& a : older_->adjLabels_[ia]) {
       labels.insert(a.label);
@@ -1590,7 +1876,9 @@ void AllNodesRouteTable::mplsDelta(
     DecisionRouteUpdate& u) const {
   for (const int32_t label : labels) {
     auto ne = mplsEntry(i, r, label);
-    auto oe = ia != SPF_MAP_NONE ? older_->mplsEntry(ia, o, label) : std::nullopt;
+    auto oe = topoDelta_ ? mplsEntryWith(i, o, label, prevAdjLabels_[i])
+        : ia != SPF_MAP_NONE ? older_->mplsEntry(ia, o, label)
+                             : std::nullopt;
     if (ne && (!oe || !(*oe == *ne))) {
       u.mplsRoutesToUpdate.push_back(std::move(*ne));
     } else if (!ne && oe) {
@@ -1639,6 +1927,10 @@ DecisionRouteUpdate AllNodesRouteTable::delta(const std::string& node) const {
   unicastDelta(i, r, cols.data(), cols.size(), gone.data(), gone.size(), u);
   if (!labels.empty()) {
     const uint32_t ia = rowOf_[i];
+    if (topoDelta_) {
+      mplsDelta(i, r, ia, C ? fetchPrevRow(i) : Row{}, labels, u);
+      return u;
+    }
     const size_t Ca = older_->numCols();
     const Row o = ia != SPF_MAP_NONE && Ca ? older_->fetchRow(ia) : Row{};
     mplsDelta(i, r, ia, o, labels, u);
@@ -1719,6 +2011,8 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
 
   // ---- MPLS candidates of every node (the labels delta() compares) and the
   // cells mplsEntry reads for them: every column of the label, in both tables
+  // (after applyTopologyChanges the older side is this table's previous cells)
+  const AllNodesRouteTable* const old = topoDelta_ ? this : older_;
   std::vector<std::vector<int32_t>> labelsOf(V);
   std::vector<std::vector<uint32_t>> colsN(V), colsO(V);
   const unsigned threads = hostThreads(V, 64);
@@ -1733,7 +2027,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
         colsN[i].insert(colsN[i].end(), lc->second.begin(), lc->second.end());
       }
       if (hasOld) {
-        if (auto lc = older_->labelCols_.find(label); lc != older_->labelCols_.end()) {
+        if (auto lc = old->labelCols_.find(label); lc != old->labelCols_.end()) {
           colsO[i].insert(colsO[i].end(), lc->second.begin(), lc->second.end());
         }
       }
@@ -1769,16 +2063,17 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
     c.best.resize(n);
     c.links.resize(c.lwPos[V]);
     c.lmet.resize(c.lmPos[V]);
-    if (int s = spf_route_table_fetch_cells(
-            t.table_.get(), n, c.rows.data(), c.cols.data(), c.metric.data(), c.best.data(),
-            c.links.data(), lfa_ ? c.lmet.data() : nullptr);
+    const auto fetch = older && topoDelta_ ? spf_route_table_fetch_cells_prev
+                                           : spf_route_table_fetch_cells;
+    if (int s = fetch(t.table_.get(), n, c.rows.data(), c.cols.data(), c.metric.data(),
+                      c.best.data(), c.links.data(), lfa_ ? c.lmet.data() : nullptr);
         s != SPF_OK) {
       tableFailure("spf_route_table_fetch_cells", s);
     }
     return c;
   };
   const Cells cn = gather(*this, colsN, false);
-  const Cells co = older_ ? gather(*older_, colsO, true) : Cells{}; // (null: no candidates)
+  const Cells co = old ? gather(*old, colsO, true) : Cells{}; // (null: no candidates)
   const auto t3 = Clock::now();
 
   // a sparse Row over cells [k0, k1) of one node in a cell list
@@ -1835,7 +2130,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
                         cn.lmet.data() + cn.lmPos[i]);
     Row ro;
     if (hasOld) {
-      ro = view(*older_, ia, co.cols.data() + b0, co.metric.data() + b0, co.best.data() + b0,
+      ro = view(*old, ia, co.cols.data() + b0, co.metric.data() + b0, co.best.data() + b0,
                 (size_t)(co.off[i + 1] - b0), co.links.data() + co.lwPos[i],
                 co.lmet.data() + co.lmPos[i]);
     }

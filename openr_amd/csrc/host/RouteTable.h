@@ -30,7 +30,7 @@
 //
 // The table owns its device graph, query and rows (a snapshot): it stays
 // valid across later LinkState changes and answers for the topology it was
-// built from.
+// built from, or the one its last applyTopologyChanges was given.
 #pragma once
 
 #include <algorithm>
@@ -50,6 +50,16 @@
 #include "openr_spf.h"
 
 namespace openr {
+
+// The rows spf_route_table_refresh_rows must list after a metric change that
+// keeps the CSR layout (row / col: the CSR; affected[i]: spf_table_screen's
+// answer for node i's SPF row; changedTails: the tails of the half-edges whose
+// metric differs).  Without LFA the affected rows; with it also every row with
+// an affected neighbour and the tails themselves -- an LFA cell reads the
+// metric of every own link and the neighbours' rows.  Ascending, host only.
+std::vector<uint32_t> routeRefreshRowList(
+    const std::vector<uint8_t>& affected, const std::vector<uint32_t>& row,
+    const std::vector<uint32_t>& col, const std::vector<uint32_t>& changedTails, bool lfa);
 
 class AllNodesRouteTable {
  public:
@@ -194,8 +204,8 @@ class AllNodesRouteTable {
 
   // Prefix changes in place (PrefixState::updatePrefixDatabase's changed
   // sets, several merged if wanted; `ps` is the state now).  The topology is
-  // this table's snapshot: the caller asserts no link or node changed since
-  // it was built.  Every changed prefix is rescanned by the constructor's
+  // this table's: the one it was built from, or the one of its last
+  // applyTopologyChanges.  Every changed prefix is rescanned by the constructor's
   // rules (scanPrefix) and, all in ONE spf_route_table_patch_columns:
   //   served before and now: its column gets the new announcers (announcers
   //     on both sides whose PrefixEntry differs are the column's dirty list);
@@ -225,6 +235,37 @@ class AllNodesRouteTable {
   // Returns the changed routes per node, id order.
   std::vector<uint32_t> applyPrefixChanges(
       const PrefixState& ps, const std::unordered_set<thrift::IpPrefix>& changed);
+  // Topology changes that keep the CSR layout, in place: link metrics and
+  // node overload (drain) bits, the common churn.  `ls` is the area's
+  // LinkState now.  Throws std::invalid_argument before anything is touched
+  // for a table built with borderNodes or bgpColumns (host-selected BGP
+  // columns depend on the drain filter and on reachability), ls.engine().exact,
+  // another area, node names, CSR row / col / rev / link ids or Link identities
+  // that differ from the table's (a link down or up, a node joined or gone:
+  // those need a fresh table and the mapped diff), or a node label that
+  // differs (the label columns would move).  Otherwise: the edge deltas
+  // (spf_graph_diff) and the overload bits choose the rows -- every row when
+  // an overload bit flipped (the drained filter of every column the node
+  // announces), else the rows spf_table_screen finds affected on the resident
+  // SPF rows, closed by routeRefreshRowList -- the table's own graph is patched
+  // (spf_graph_patch_metrics, spf_graph_set_transit), a new all-sources query
+  // runs on it (the whole SPF: repairing only the affected rows is not done
+  // here) and spf_route_table_refresh_rows recomputes the listed rows and
+  // keeps the cells it replaced.  Adjacency labels are collected again.
+  // Afterwards routes(), mplsRoutes(), countRoutes() describe the new
+  // topology, changedSplit / delta / deltas give this call's delta with no
+  // older table (MPLS: mplsEntry over the new cells against the same rule
+  // over the previous cells and the previous adjacency labels), diff() works
+  // with this table on either side, and applyPrefixChanges may follow.
+  // A device failure after the graph was patched throws std::runtime_error and
+  // leaves the table unusable (its graph, rows and cells no longer agree).
+  // Returns the changed routes per node (unicast and node-label columns), id
+  // order.
+  std::vector<uint32_t> applyTopologyChanges(const LinkState& ls);
+  // device time of the last applyTopologyChanges' refresh kernel (its SPF: spfMs)
+  float refreshMs() const { return refreshMs_; }
+  // rows the last applyTopologyChanges listed
+  size_t refreshRows() const { return refreshRows_; }
   // columns applyPrefixChanges can still give away
   size_t freeColumns() const { return freeList_.size(); }
   // free selected columns (spareSelectedColumns and freed ones)
@@ -276,6 +317,11 @@ class AllNodesRouteTable {
   // the MPLS entry of `label` at node i: the node-label winner, else the
   // first adjacency label of that value
   std::optional<RibMplsEntry> mplsEntry(uint32_t i, const Row& r, int32_t label) const;
+  struct AdjLabel;
+  std::optional<RibMplsEntry> mplsEntryWith(
+      uint32_t i, const Row& r, int32_t label, const std::vector<AdjLabel>& adj) const;
+  // row i as it was before the last applyTopologyChanges (spf_route_table_fetch_cells_prev)
+  Row fetchPrevRow(uint32_t i) const;
   std::optional<RibMplsEntry> nodeLabelEntry(uint32_t i, const Row& r, int32_t label) const;
   // The delta of one node from the last diff, shared by delta(node) and
   // deltas().  `cols` are the node's changed columns, `gone` its set bits of
@@ -311,6 +357,10 @@ class AllNodesRouteTable {
   std::vector<std::string> names_;
   std::unordered_map<std::string, uint32_t> ids_;
   std::vector<uint32_t> row_;                 // CSR row offsets of the snapshot
+  // the rest of the CSR (applyTopologyChanges: layout check and edge deltas)
+  std::vector<uint32_t> col_, rev_, linkId_;
+  std::vector<uint64_t> metric_;
+  uint32_t numLinks_{0};
   std::vector<std::shared_ptr<Link>> halfLink_; // half-edge -> Link
   std::vector<thrift::IpPrefix> prefixes_;
   std::vector<std::vector<Announcer>> announcers_;
@@ -390,6 +440,11 @@ class AllNodesRouteTable {
   std::unordered_map<thrift::IpPrefix, uint32_t> colOfPrefix_; // served prefix -> column
   bool hasBorder_{false};
   bool patchDelta_{false}; // the last delta is applyPrefixChanges' (older_ is null)
+  // the last delta is applyTopologyChanges' (older_ is null): the older side
+  // is this table's previous cells and prevAdjLabels_
+  bool topoDelta_{false};
+  float refreshMs_{0};
+  size_t refreshRows_{0};
   float patchMs_{0};
   // per node: columns of the last applyPrefixChanges whose cell changed in
   // `best` alone, between announcers with equal PrefixEntries (no route change)
@@ -426,6 +481,7 @@ class AllNodesRouteTable {
     std::string area;
   };
   std::vector<std::vector<AdjLabel>> adjLabels_;
+  std::vector<std::vector<AdjLabel>> prevAdjLabels_; // before the last applyTopologyChanges
   std::vector<int32_t> nodeLabel_; // per node id: its valid node label, else 0
   const AllNodesRouteTable* older_{nullptr};
   // the last diff(): older row of every node (SPF_MAP_NONE: none) and, when

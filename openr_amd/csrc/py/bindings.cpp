@@ -475,6 +475,10 @@ PYBIND11_MODULE(_openr_spf, m) {
       .def("next_hops", &AllSourcesTable::nextHops)
       .def_property_readonly("has_next_hops", &AllSourcesTable::hasNextHops);
 
+  // the rows applyTopologyChanges lists, from a screen result (host only)
+  m.def("route_refresh_row_list", &routeRefreshRowList, py::arg("affected"), py::arg("row_ptr"),
+        py::arg("col"), py::arg("changed_tails"), py::arg("lfa"));
+
   py::class_<AllNodesRouteTable>(m, "AllNodesRouteTable")
       .def(py::init([](const AreaMapHolder& areas, const std::string& area, const PrefixState& ps,
                        bool enableV4, bool lfa, bool bgpColumns, bool bgpDryRun,
@@ -506,6 +510,14 @@ PYBIND11_MODULE(_openr_spf, m) {
              return t.applyPrefixChanges(ps, changed);
            },
            py::arg("prefix_state"), py::arg("prefixes"))
+      .def("apply_topology_changes",
+           [](AllNodesRouteTable& t, const AreaMapHolder& areas, const std::string& area) {
+             // areas[area]: the area's LinkState now (read during the call only)
+             return t.applyTopologyChanges(areas.map.at(area));
+           },
+           py::arg("areas"), py::arg("area"))
+      .def_property_readonly("refresh_ms", &AllNodesRouteTable::refreshMs)
+      .def_property_readonly("refresh_rows", &AllNodesRouteTable::refreshRows)
       .def_property_readonly("free_columns", &AllNodesRouteTable::freeColumns)
       .def_property_readonly("free_selected_columns", &AllNodesRouteTable::freeSelectedColumns)
       .def_property_readonly("patch_ms", &AllNodesRouteTable::patchMs)

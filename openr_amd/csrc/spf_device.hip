@@ -6924,6 +6924,125 @@ __global__ __launch_bounds__(256) void spf_route_patch_kernel(
   }
 }
 
+// In-place refresh of listed rows (spf_route_table_refresh_rows): the row-wise
+// counterpart of the patch above, for a topology change that keeps the CSR
+// layout.  For list entry r (row q = rows[r], or r itself without a list) and
+// every column p, rt_cell<false> computes the cell from the query's NEW rows
+// and masks into entry r of the previous-cell store, which is then SWAPPED
+// with the resident cell word by word where the words differ: afterwards the
+// resident row holds the new cells and the store the old ones (equal where
+// nothing moved; metric and best are always stored).  The compare is the
+// equal-layout diff's (spf_route_table_diff_kernel<false, ROUTES>, which the
+// patch rule equals without dirty lists).
+//
+// Launch shape: the full kernel's, one 256-thread workgroup per list entry
+// with the row's links staged once (rt_stage_row, kRtStage links; the unstaged
+// path of rt_cell beyond it), and no grid stride, so the one barrier is met by
+// every lane.  The column loop is rounded up to whole waves: a wave owns 64
+// consecutive columns, its bitmap word is one ballot stored by lane 0 (no
+// atomics on the bitmap, which is cleared for the unlisted rows only), lanes
+// past P vote false, and the row's count is the popcount of the wave's words.
+struct RouteRefreshArgs {
+  RouteTableArgs t;       // the table's arrays over the NEW query; metric_out .. lmet_out resident
+  const uint32_t* rows;   // [nrows] distinct query rows, or null: entry r is row r
+  uint32_t* p_metric;     // the store: [nrows][P]
+  uint32_t* p_best;
+  uint64_t* p_links;      // entry r at p_lk_off[r], laid out like the row
+  const uint64_t* p_lk_off;
+  uint32_t* p_lmet;       // (LFA) entry r at p_lm_off[r]
+  const uint64_t* p_lm_off;
+  uint64_t* bits;         // [nq * pw], cleared
+  uint32_t* count;        // [nq], zeroed
+  uint32_t nrows, pw, routes_only;
+};
+
+__global__ __launch_bounds__(256) void spf_route_refresh_kernel(RouteRefreshArgs ra) {
+  __shared__ uint32_t st_nbr[kRtStage];
+  __shared__ uint32_t st_w[kRtStage];
+  __shared__ uint32_t st_slot[kRtStage];
+  __shared__ uint32_t st_slotall[kRtStage];
+  __shared__ uint32_t st_dns[kRtStage];
+  const RouteTableArgs& a = ra.t;
+  const uint32_t r = blockIdx.x; // < nrows: the grid is the list
+  const uint32_t q = ra.rows ? ra.rows[r] : r;
+  const uint32_t s = a.src[q];
+  const uint32_t* d = a.dist + (size_t)q * a.Vp;
+  const uint32_t e0 = a.row[s], deg = a.row[s + 1] - e0;
+  const bool staged = deg <= kRtStage;
+  if (staged) {
+    rt_stage_row(a, s, d, e0, deg, threadIdx.x, 256, st_nbr, st_w, st_slot, st_slotall, st_dns);
+  }
+  __syncthreads();
+  const uint8_t* nhq = a.nh + a.nh_off[q];
+  const uint32_t W = a.nh_w[q], NB = a.nh_b[q];
+  const uint32_t WL = (deg + 63) / 64;
+  uint64_t* slk = ra.p_links + ra.p_lk_off[r];
+  uint32_t* slm = a.lfa ? ra.p_lmet + ra.p_lm_off[r] : nullptr;
+  uint64_t* lk = a.link_out + a.lk_off[q];
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t n = 0;
+  for (uint32_t p0 = threadIdx.x - lane; p0 < a.P; p0 += 256) { // wave-uniform
+    const uint32_t p = p0 + lane;
+    bool ch = false;
+    if (p < a.P) {
+      uint32_t nm, nbest;
+      uint64_t* nl = slk + (size_t)p * WL;
+      uint32_t* nlm = slm ? slm + (size_t)p * deg : nullptr;
+      rt_cell<false>(a, q, p, s, d, nhq, W, NB, e0, deg, WL, staged, st_nbr, st_w, st_slot,
+                     st_slotall, st_dns, false, ~0u, kInf32,
+                     [&](uint32_t*& metric_o, uint32_t*& best_o, uint64_t*& lkp, uint32_t*& lm) {
+                       metric_o = &nm;
+                       best_o = &nbest;
+                       lkp = nl;
+                       lm = nlm;
+                     });
+      const size_t o = (size_t)q * a.P + p;
+      uint64_t* ol = lk + (size_t)p * WL;
+      uint32_t* olm = slm ? a.lmet_out + a.lm_off[q] + (size_t)p * deg : nullptr;
+      const uint32_t om = a.metric_out[o], ob = a.best_out[o];
+      if (om == kInf32 || nm == kInf32) {
+        ch = om != nm;
+      } else {
+        ch = (om != nm && !ra.routes_only) || ob != nbest;
+      }
+      ra.p_metric[(size_t)r * a.P + p] = om;
+      ra.p_best[(size_t)r * a.P + p] = ob;
+      if (om != nm) {
+        a.metric_out[o] = nm;
+      }
+      if (ob != nbest) {
+        a.best_out[o] = nbest;
+      }
+      // (a cell without a route has clear link words and kInf32 link metrics:
+      // with one side routeless the words below differ only where ch is set)
+      for (uint32_t k = 0; k < WL; ++k) {
+        const uint64_t x = nl[k], y = ol[k];
+        if (x != y) {
+          ol[k] = x;
+          nl[k] = y;
+          ch = true;
+        }
+      }
+      for (uint32_t j = 0; olm && j < deg; ++j) {
+        const uint32_t x = nlm[j], y = olm[j];
+        if (x != y) {
+          olm[j] = x;
+          nlm[j] = y;
+          ch = true;
+        }
+      }
+    }
+    const uint64_t word = __ballot(ch);
+    if (lane == 0) {
+      ra.bits[(size_t)q * ra.pw + (p0 >> 6)] = word;
+      n += __popcll(word);
+    }
+  }
+  if (lane == 0 && n) {
+    atomicAdd(&ra.count[q], n);
+  }
+}
+
 // BGP best path per node with the IGP cost in the metric vector
 // (spf_route_table_create_sel; SpfSolverImpl::runBestPathSelectionBgp,
 // Decision.cpp:714-803, with bgpUseIgpMetric :746-766, then selectEcmpBgp
@@ -15133,6 +15252,17 @@ struct spf_route_table {
   uint32_t pt_wave = 0;
   DevEvent evp0, evp1;
   bool patched = false;
+  // spf_route_table_refresh_rows: the previous-cell store (grow-only; entry r
+  // = the cells of listed row rf_rows[r] before the refresh, laid out like the
+  // row), the slot of every row in it (kInf32: not listed, its resident cells
+  // are its previous ones) and the entries' offsets; evr0 .. evr1 time the
+  // kernel.  rf_valid: a refresh is current (no run or patch since)
+  DevBuf<uint32_t> d_rf_rows, d_rf_metric, d_rf_best, d_rf_lmet;
+  DevBuf<uint64_t> d_rf_links, d_rf_lk_off, d_rf_lm_off;
+  std::vector<uint32_t> rf_rows, rf_slot;
+  std::vector<uint64_t> rf_lk_off, rf_lm_off; // [rf_rows.size() + 1]
+  DevEvent evr0, evr1;
+  bool refreshed = false, rf_valid = false;
 };
 
 namespace {
@@ -15434,6 +15564,7 @@ int spf_route_table_run(spf_route_table* t) {
   t->ran = true;
   ++t->epoch; // the bitmaps of an earlier diff describe the rows just overwritten
   t->diffed = false;
+  t->rf_valid = false;
   return SPF_OK;
 }
 
@@ -16177,6 +16308,7 @@ static int route_patch_apply(spf_route_table* t, const spf_route_patch* p,
   t->mapped = true; // spf_route_table_changed_gone: no gone columns
   t->gone_n = 0;
   t->patched = true;
+  t->rf_valid = false; // the previous cells of an earlier refresh are not these cells'
   if (nq == 0) {
     return SPF_OK;
   }
@@ -16454,10 +16586,13 @@ int spf_route_table_delta_fetch_igp(spf_route_table* t, uint32_t* igp) {
 } // extern "C"
 
 namespace {
-// spf_route_table_fetch_cells (igp null) and _fetch_cells_igp (igp alone)
+// spf_route_table_fetch_cells (igp null) and _fetch_cells_igp (igp alone).
+// `prev`: the cells come from the previous-cell store of the last refresh and
+// rows[] holds store entries (spf_route_table_fetch_cells_prev).
 int fetch_cells_impl(
     spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* metric,
-    uint32_t* best, uint64_t* links, uint32_t* link_metrics, uint32_t* igp_out, bool igp) {
+    uint32_t* best, uint64_t* links, uint32_t* link_metrics, uint32_t* igp_out, bool igp,
+    bool prev = false) {
   if (!t) {
     return fail(SPF_E_INVALID, "null table");
   }
@@ -16474,7 +16609,8 @@ int fetch_cells_impl(
     return fail(SPF_E_INVALID, "null argument");
   }
   // ---- validation (host): every index the kernels follow is in range
-  const uint32_t nq = t->q->nq, P = t->P;
+  const uint32_t nq = prev ? (uint32_t)t->rf_rows.size() : t->q->nq, P = t->P;
+  const std::vector<uint64_t>& lk_off = prev ? t->rf_lk_off : t->lk_off;
   std::vector<uint64_t> pos(igp ? 0 : t->lfa ? 2 * n : n);
   uint64_t nl = 0, nm = 0;
   for (uint64_t k = 0; k < n; ++k) {
@@ -16485,10 +16621,10 @@ int fetch_cells_impl(
       continue; // one word per cell: no link positions
     }
     pos[k] = nl;
-    nl += (t->lk_off[rows[k] + 1] - t->lk_off[rows[k]]) / P;
+    nl += (lk_off[rows[k] + 1] - lk_off[rows[k]]) / P;
     if (t->lfa) {
       pos[n + k] = nm;
-      nm += t->deg[rows[k]];
+      nm += t->deg[prev ? t->rf_rows[rows[k]] : rows[k]];
     }
   }
   if ((nl && !links) || (nm && !link_metrics)) {
@@ -16514,7 +16650,9 @@ int fetch_cells_impl(
   const uint32_t maxGrid = (uint32_t)g->num_cus * 8;
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, maxGrid);
   SPF_LAUNCH(spf_route_cells_gather_kernel, dim3(grid), dim3(256), 0, g->stream, t->d_gc_idx,
-             t->d_gc_idx + n, t->d_gc_pos, n, P, t->d_metric, t->d_best, t->d_links, t->d_lk_off,
+             t->d_gc_idx + n, t->d_gc_pos, n, P, prev ? t->d_rf_metric.p : t->d_metric.p,
+             prev ? t->d_rf_best.p : t->d_best.p, prev ? t->d_rf_links.p : t->d_links.p,
+             prev ? t->d_rf_lk_off.p : t->d_lk_off.p,
              igp ? nullptr : t->d_gc_out.p, t->d_gc_out + n, t->d_gc_links, t->d_sel_of,
              t->d_sel_igp, t->S, igp ? t->d_gc_out + 2 * n : nullptr);
   HIP_TRY(hipGetLastError());
@@ -16527,7 +16665,8 @@ int fetch_cells_impl(
   if (nm) {
     const uint32_t wgrid = (uint32_t)std::min<uint64_t>((n + 3) / 4, maxGrid);
     SPF_LAUNCH(spf_route_cells_gather_lmet_kernel, dim3(wgrid), dim3(256), 0, g->stream,
-               t->d_gc_idx, t->d_gc_idx + n, t->d_gc_pos + n, n, P, t->d_lmet, t->d_lm_off,
+               t->d_gc_idx, t->d_gc_idx + n, t->d_gc_pos + n, n, P,
+               prev ? t->d_rf_lmet.p : t->d_lmet.p, prev ? t->d_rf_lm_off.p : t->d_lm_off.p,
                t->d_gc_lmet);
     HIP_TRY(hipGetLastError());
   }
@@ -16557,6 +16696,253 @@ int spf_route_table_fetch_cells_igp(
     spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* igp) {
   SPF_ABI_RANGE("spf_route_table_fetch_cells_igp");
   return fetch_cells_impl(t, n, rows, cols, nullptr, nullptr, nullptr, nullptr, igp, true);
+}
+
+int spf_route_table_refresh_rows(
+    spf_route_table* t, spf_query* q, uint32_t num_rows, const uint32_t* rows, uint32_t* changed) {
+  SPF_ABI_RANGE("spf_route_table_refresh_rows");
+  if (!t || !q) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  if (!t->ran) {
+    return fail(SPF_E_INVALID, "table has not run");
+  }
+  if (!q->ran) {
+    return fail(SPF_E_INVALID, "the query has not run");
+  }
+  spf_query* q0 = t->q;
+  spf_graph* g = q0->g;
+  if (q->g != g) {
+    return fail(SPF_E_INVALID, "the query is over another graph than the table's");
+  }
+  if (!(q->flags & SPF_F_NEXTHOPS) || (q->flags & SPF_F_UNIT_METRIC) || q->has_ign) {
+    return fail(SPF_E_INVALID, "route tables need a metric query with next hops and no ignore lists");
+  }
+  if (rows64(q)) {
+    return fail(SPF_E_UNSUPPORTED, "64-bit distance rows");
+  }
+  if (t->S) {
+    return fail(SPF_E_UNSUPPORTED, "a table with selected columns (their selection words follow "
+                                   "the rows too: recreate the table)");
+  }
+  const uint32_t nq = q0->nq, P = t->P, pw = (P + 63) / 64;
+  HIP_TRY(hipSetDevice(g->device));
+  if (q != q0) {
+    if (q->nq != nq) {
+      return fail(SPF_E_INVALID, "the query's sources differ from the table's");
+    }
+    std::vector<uint32_t> sa(nq), sb(nq);
+    if (nq) {
+      HIP_TRY(hipMemcpy(sa.data(), q0->d_src, (size_t)nq * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(sb.data(), q->d_src, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    }
+    if (sa != sb) {
+      return fail(SPF_E_INVALID, "the query's sources differ from the table's");
+    }
+    // (same graph, same sources: the masks have the table query's widths)
+    if (q->nh_w != q0->nh_w || q->Vp != q0->Vp) {
+      return fail(SPF_E_INVALID, "the query's row layout differs from the table's");
+    }
+  }
+  const uint32_t nr = rows ? num_rows : nq;
+  std::vector<uint32_t> list(nr), slot(nq, kInf32);
+  for (uint32_t r = 0; r < nr; ++r) {
+    const uint32_t i = rows ? rows[r] : r;
+    if (i >= nq || slot[i] != kInf32) {
+      return fail(SPF_E_INVALID, "row out of range or listed twice");
+    }
+    slot[i] = r;
+    list[r] = i;
+  }
+  std::vector<uint64_t> lk(nr + 1, 0), lm(nr + 1, 0);
+  for (uint32_t r = 0; r < nr; ++r) {
+    lk[r + 1] = lk[r] + (t->lk_off[list[r] + 1] - t->lk_off[list[r]]);
+    lm[r + 1] = lm[r] + (t->lm_off[list[r] + 1] - t->lm_off[list[r]]);
+  }
+  // every check is done; the store's arrays may be replaced from here on, so
+  // an earlier refresh's previous cells are given up first
+  t->rf_valid = false;
+  if (nq) {
+    HIP_TRY(t->d_count.reserve(nq));
+    HIP_TRY(t->d_diff.reserve((size_t)nq * pw));
+    if (!t->evr0.e && (t->evr0.create() != hipSuccess || t->evr1.create() != hipSuccess)) {
+      return fail(SPF_E_DEVICE, "hipEventCreate");
+    }
+  }
+  if (nr && P) {
+    if (t->d_rf_metric.reserve((size_t)nr * P) != hipSuccess ||
+        t->d_rf_best.reserve((size_t)nr * P) != hipSuccess ||
+        t->d_rf_links.reserve((size_t)lk[nr]) != hipSuccess ||
+        t->d_rf_lmet.reserve((size_t)lm[nr]) != hipSuccess) {
+      return fail(SPF_E_NOMEM, "previous-cell store");
+    }
+  }
+  // earlier fetches from the store (stream order) end before its lists move
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  if (int st = t->d_rf_rows.upload(list.data(), nr); st != SPF_OK) {
+    return st;
+  }
+  if (int st = t->d_rf_lk_off.upload(lk.data(), lk.size()); st != SPF_OK) {
+    return st;
+  }
+  if (int st = t->d_rf_lm_off.upload(lm.data(), lm.size()); st != SPF_OK) {
+    return st;
+  }
+  // accepted
+  t->rf_rows = std::move(list);
+  t->rf_slot = std::move(slot);
+  t->rf_lk_off = std::move(lk);
+  t->rf_lm_off = std::move(lm);
+  if (q != q0) {
+    q0->live_tables.fetch_sub(1, std::memory_order_relaxed);
+    q->live_tables.fetch_add(1, std::memory_order_relaxed);
+    t->q = q;
+  }
+  ++t->epoch;
+  t->diffed = true;
+  t->diff_mapped_last = false;
+  t->mapped = true; // spf_route_table_changed_gone: no gone columns
+  t->gone_n = 0;
+  t->refreshed = true;
+  if (nq == 0) {
+    t->rf_valid = true;
+    return SPF_OK;
+  }
+  HIP_TRY(hipMemsetAsync(t->d_count, 0, (size_t)nq * 4, g->stream));
+  if (pw) {
+    HIP_TRY(hipMemsetAsync(t->d_diff, 0, (size_t)nq * pw * 8, g->stream));
+  }
+  HIP_TRY(hipEventRecord(t->evr0, g->stream));
+  if (nr && P) {
+    RouteRefreshArgs ra{};
+    RouteTableArgs& a = ra.t;
+    a.row = g->d_row;
+    a.col = g->d_col;
+    a.wout = g->d_wout;
+    a.slot = g->d_slot;
+    a.trbits = g->d_tr;
+    a.src = q->d_src;
+    a.dist = (const uint32_t*)q->d_dist;
+    a.nh = q->d_nhb;
+    a.nh_off = q->d_nhb_off;
+    a.nh_b = q->d_nh_b;
+    a.nh_w = q->d_nh_w;
+    a.ann_off = t->d_ann_off;
+    a.ann = t->d_ann;
+    a.lk_off = t->d_lk_off;
+    a.metric_out = t->d_metric;
+    a.best_out = t->d_best;
+    a.link_out = t->d_links;
+    a.row_of = t->d_row_of;
+    a.lm_off = t->d_lm_off;
+    a.lmet_out = t->d_lmet;
+    a.lfa = t->lfa ? 1u : 0u;
+    a.Vp = q->Vp;
+    a.P = P;
+    a.nq = nq;
+    ra.rows = rows ? t->d_rf_rows.p : nullptr;
+    ra.p_metric = t->d_rf_metric;
+    ra.p_best = t->d_rf_best;
+    ra.p_links = t->d_rf_links;
+    ra.p_lk_off = t->d_rf_lk_off;
+    ra.p_lmet = t->d_rf_lmet;
+    ra.p_lm_off = t->d_rf_lm_off;
+    ra.bits = t->d_diff;
+    ra.count = t->d_count;
+    ra.nrows = nr;
+    ra.pw = pw;
+    ra.routes_only = t->diff_routes ? 1u : 0u;
+    SPF_LAUNCH(spf_route_refresh_kernel, dim3(nr), dim3(256), 0, g->stream, ra);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(t->evr1, g->stream));
+  if (changed) {
+    HIP_TRY(hipMemcpyAsync(changed, t->d_count, (size_t)nq * 4, hipMemcpyDeviceToHost, g->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  t->rf_valid = true;
+  return SPF_OK;
+}
+
+int spf_route_table_refresh_elapsed_ms(spf_route_table* t, float* ms) {
+  if (!t || !ms || !t->refreshed) {
+    return fail(SPF_E_INVALID, "no refresh to time");
+  }
+  *ms = 0.f;
+  if (!t->evr1.e) {
+    return SPF_OK;
+  }
+  HIP_TRY(hipEventSynchronize(t->evr1));
+  HIP_TRY(hipEventElapsedTime(ms, t->evr0, t->evr1));
+  return SPF_OK;
+}
+
+int spf_route_table_fetch_cells_prev(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* metric,
+    uint32_t* best, uint64_t* links, uint32_t* link_metrics) {
+  SPF_ABI_RANGE("spf_route_table_fetch_cells_prev");
+  if (!t) {
+    return fail(SPF_E_INVALID, "null table");
+  }
+  if (!t->rf_valid) {
+    return fail(SPF_E_INVALID, "no refresh is current on this table");
+  }
+  if (n == 0) {
+    return SPF_OK;
+  }
+  if (!rows || !cols || !metric || !best) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  // cells of listed rows come from the store, the others from the resident
+  // rows: two gathers, put back in list order
+  const uint32_t nq = t->q->nq, P = t->P;
+  std::vector<uint64_t> idx[2], lpos(n), mpos(n);
+  std::vector<uint32_t> rr[2], cc[2];
+  uint64_t nl = 0, nm = 0;
+  for (uint64_t k = 0; k < n; ++k) {
+    if (rows[k] >= nq || cols[k] >= P) {
+      return fail(SPF_E_INVALID, "cell row or column out of range");
+    }
+    const uint32_t sl = t->rf_slot[rows[k]];
+    const int w = sl != kInf32;
+    idx[w].push_back(k);
+    rr[w].push_back(w ? sl : rows[k]);
+    cc[w].push_back(cols[k]);
+    lpos[k] = nl;
+    mpos[k] = nm;
+    nl += (t->lk_off[rows[k] + 1] - t->lk_off[rows[k]]) / P;
+    nm += t->lfa ? t->deg[rows[k]] : 0;
+  }
+  if ((nl && !links) || (nm && !link_metrics)) {
+    return fail(SPF_E_INVALID, "null links or link_metrics");
+  }
+  for (int w = 0; w < 2; ++w) {
+    const uint64_t m = idx[w].size();
+    if (!m) {
+      continue;
+    }
+    std::vector<uint32_t> pm(m), pb(m), plm(nm ? nm : 1);
+    std::vector<uint64_t> pl(nl ? nl : 1);
+    if (int st = fetch_cells_impl(t, m, rr[w].data(), cc[w].data(), pm.data(), pb.data(),
+                                  pl.data(), plm.data(), nullptr, false, w == 1);
+        st != SPF_OK) {
+      return st;
+    }
+    uint64_t al = 0, am = 0;
+    for (uint64_t j = 0; j < m; ++j) {
+      const uint64_t k = idx[w][j];
+      metric[k] = pm[j];
+      best[k] = pb[j];
+      const uint64_t W = (t->lk_off[rows[k] + 1] - t->lk_off[rows[k]]) / P;
+      std::copy_n(pl.begin() + al, W, links + lpos[k]);
+      al += W;
+      if (t->lfa) {
+        std::copy_n(plm.begin() + am, t->deg[rows[k]], link_metrics + mpos[k]);
+        am += t->deg[rows[k]];
+      }
+    }
+  }
+  return SPF_OK;
 }
 
 } // extern "C"
