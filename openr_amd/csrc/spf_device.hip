@@ -4087,8 +4087,20 @@ struct NlSub { // GS (or fewer) sources with one neighbour list
   uint32_t m0, cnt, n, lo, B, pad;
 };
 struct NlMem {
-  uint32_t q, pad;
+  uint32_t q;
+  uint32_t plo; // wide groups: first NlEnt of the member's private blocks
   uint64_t nhb_off;
+};
+// Wide sources (whole-word mask rows, B = 8 * Wm) whose neighbour lists have
+// the same length and agree on at least half of their 8-entry-aligned
+// blocks: the agreeing ("shared", bit b of shmask) blocks are stored once
+// for the group at lo, packed in block order, and their level words are
+// loaded once for every member; the other ("private") blocks are stored per
+// member at NlMem::plo, packed the same way.  A partial last block is padded
+// to 8 entries.
+struct NlWide {
+  uint32_t m0, cnt, n, lo, B, Wm;
+  uint32_t shmask, pad;
 };
 struct NlV2Args {
   const NlSolo* solo;
@@ -4096,6 +4108,8 @@ struct NlV2Args {
   const NlMem* mem;
   const NlEnt* ent;
   uint32_t nsolo, nsub;
+  const NlWide* wide = nullptr; // wide groups (OPENR_NL_WIDE_GROUPS=0: none); never with trit
+  uint32_t nwide = 0;
   // bytes of the level table (< 2^31: the kernel's buffer descriptor)
   uint32_t lvl_bytes;
   // round 6: 2-bit level rows (spf_lvl_trit_kernel: level mod 3, 3 =
@@ -4112,6 +4126,11 @@ struct NlV2Args {
 };
 constexpr uint32_t kNlGS = 8;  // sources per group block
 constexpr uint32_t kNlGN = 16; // neighbours of a group source (one mask word, B <= 2)
+// Members of a wide group.  A member's finished mask words stay in registers
+// until its turn at the wave's one LDS tile (8 VGPRs per member and word), so
+// the size is what the kernel's 80-VGPR budget (6 waves per SIMD) leaves:
+// two members, the first of which writes its words to the tile as they finish
+constexpr uint32_t kNlWS = 2;
 
 __device__ __forceinline__ bool nl_transit(const uint32_t* trbits, uint32_t f) {
   return (trbits[f >> 5] >> (f & 31)) & 1u;
@@ -4316,6 +4335,9 @@ __global__ __launch_bounds__(256) void spf_lvl_trit_kernel(LvlTritArgs a) {
   *reinterpret_cast<uint32_t*>(a.trit + (size_t)r * (a.Vp8 / 4) + 4u * c) = out;
 }
 
+__device__ __forceinline__ void nl_tile_flush(uint8_t* row, uint32_t vbase, uint32_t V,
+                                              uint32_t Wm, const uint64_t* tile, uint32_t lane);
+
 // Mask rows of B = 8 * Wm bytes per node, one wave's 256 nodes: a lane holds
 // 4 consecutive nodes (32 * Wm contiguous bytes), so storing from registers
 // puts 16-byte pieces 32 * Wm bytes apart in every wave instruction (partial
@@ -4335,6 +4357,12 @@ __device__ __forceinline__ void nl_store_wide(uint8_t* row, uint32_t vbase, uint
       }
     }
   }
+  nl_tile_flush(row, vbase, V, Wm, tile, lane);
+}
+
+// The wave's filled tile (node-major, Wm words per node) -> the mask row
+__device__ __forceinline__ void nl_tile_flush(uint8_t* row, uint32_t vbase, uint32_t V,
+                                              uint32_t Wm, const uint64_t* tile, uint32_t lane) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -4649,14 +4677,200 @@ __device__ __forceinline__ void nl_v2_group(const NhLevelsArgs& a, const NlV2Arg
   }
 }
 
-// One block per (item, chunk), item-major; the group items are spread evenly
-// among the solo items, so VALU-heavy solo blocks and store-heavy group
-// blocks are resident together.  A BFS deeper than 254 levels leaves
+// A wide group (NlWide) on one chunk, one 256-node segment per wave: the
+// level words of a shared block are loaded once and compared against every
+// member's targets; a private block is loaded per member.  Same compares,
+// masks and distance rows as nl_v2_solo.  The first member's mask words go
+// to the wave's tile as they finish; the others wait in registers for the
+// tile (nl_store_wide).
+template <uint32_t T, bool SH>
+__device__ __forceinline__ void nl_v2_wide_group(const NhLevelsArgs& a, const NlV2Args& v,
+                                                 uint32_t k, uint32_t c, uint64_t* tile,
+                                                 __amdgpu_buffer_rsrc_t rs) {
+  const nl_cptr<NlWide> dp = nl_const(v.wide) + k;
+  const uint32_t m0 = dp->m0, cnt = dp->cnt, n = dp->n, lo = dp->lo, Wm = dp->Wm,
+                 shmask = dp->shmask;
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t vbase = c * (4 * T) + wv * 256;
+  if (vbase >= a.V) {
+    return; // wave-uniform
+  }
+  const uint32_t v0 = vbase + 4 * lane;
+  const bool active = v0 < a.V;
+  const nl_cptr<NlEnt> sent = nl_const(v.ent + lo);
+  const nl_cptr<NlMem> mem = nl_const(v.mem + m0);
+  uint32_t qs[kNlWS], plo[kNlWS];
+#pragma unroll
+  for (uint32_t i = 0; i < kNlWS; ++i) { // past cnt: padding, unused
+    qs[i] = __builtin_amdgcn_readfirstlane(mem[i].q);
+    plo[i] = __builtin_amdgcn_readfirstlane(mem[i].plo);
+  }
+  uint32_t ls[kNlWS], tgt[kNlWS], live[kNlWS];
+#pragma unroll
+  for (uint32_t i = 0; i < kNlWS; ++i) {
+    ls[i] = (active && i < cnt) ? nl_lvl_word(rs, v0, qs[i] * a.Vp8) : 0xFFFFFFFFu;
+    tgt[i] = ((ls[i] | 0x80808080u) - 0x01010101u) ^ (~ls[i] & 0x80808080u);
+    live[i] = 0x80808080u & ~(swar_zero_bytes(ls[i]) | swar_zero_bytes(~ls[i]));
+  }
+  auto cmp = [&](const uint32_t(&lf)[8], uint32_t i, uint32_t ntg, nl_cptr<NlEnt> e8)
+                 __attribute__((always_inline)) {
+    if constexpr (SH) {
+      const uint32_t Q = nl_s_cmp8(lf, tgt[i]);
+      return ~Q & nl_live8(live[i]) & (ntg ? nl_s_allow(ntg, e8, v0) : 0xFFFFFFFFu);
+    } else {
+      return nl_v3_cmp8(lf, tgt[i], live[i], ntg, e8, v0);
+    }
+  };
+  // one mask word of every member: P[i][g] = block g's matches (nl_v3_cmp8 layout)
+  auto word = [&](uint32_t w, uint32_t(&P)[kNlWS][8]) __attribute__((always_inline)) {
+    const uint32_t cntw = min(64u, n - min(n, 64 * w));
+    // drained neighbours: lane j tests entry 64w + j, in the group's list
+    // (shared block) or in every member's (private block)
+    const uint32_t lb = 8 * w + (lane >> 3), lbel = (1u << lb) - 1u;
+    const bool inl = 64 * w + lane < n, shb = ((shmask >> lb) & 1u) != 0;
+    const uint32_t os = 8 * __popc(shmask & lbel) + (lane & 7u);
+    const uint32_t op = 8 * __popc(~shmask & lbel) + (lane & 7u);
+    bool nt = false;
+    if (inl && shb) {
+      nt = !nl_transit(a.trbits, sent[os].node);
+    }
+    const uint64_t nts = __ballot(nt);
+    uint64_t ntp[kNlWS];
+#pragma unroll
+    for (uint32_t i = 0; i < kNlWS; ++i) {
+      bool x = false;
+      if (inl && !shb && i < cnt) {
+        x = !nl_transit(a.trbits, nl_const(v.ent + plo[i])[op].node);
+      }
+      ntp[i] = __ballot(x);
+    }
+#pragma unroll
+    for (uint32_t g = 0; g < 8; ++g) {
+#pragma unroll
+      for (uint32_t i = 0; i < kNlWS; ++i) {
+        P[i][g] = 0;
+      }
+      if (8 * g < cntw) {
+        const uint32_t bb = 8 * w + g, rem = cntw - 8 * g, bel = (1u << bb) - 1u;
+        if ((shmask >> bb) & 1u) { // wave-uniform
+          const nl_cptr<NlEnt> e8 = sent + 8 * __popc(shmask & bel);
+          uint32_t A[8];
+          nl_v3_ld8(rs, v0, a.Vp8, e8, rem, A);
+          const uint32_t ntg = (uint32_t)(nts >> (8 * g)) & 0xFFu;
+#pragma unroll
+          for (uint32_t i = 0; i < kNlWS; ++i) {
+            if (i < cnt) {
+              P[i][g] = cmp(A, i, ntg, e8);
+            }
+          }
+        } else {
+          const uint32_t po = 8 * __popc(~shmask & bel);
+#pragma unroll
+          for (uint32_t i = 0; i < kNlWS; ++i) {
+            if (i < cnt) {
+              const nl_cptr<NlEnt> e8 = nl_const(v.ent + plo[i]) + po;
+              uint32_t A[8];
+              nl_v3_ld8(rs, v0, a.Vp8, e8, rem, A);
+              const uint32_t ntg = (uint32_t)(ntp[i] >> (8 * g)) & 0xFFu;
+              P[i][g] = cmp(A, i, ntg, e8);
+            }
+          }
+        }
+        // (the scheduler otherwise hoists later blocks' loads over these
+        // compares: 104 VGPRs, 4 waves per SIMD for the whole kernel)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  };
+  auto words4 = [&](const uint32_t(&Pi)[8], uint64_t(&x)[4]) __attribute__((always_inline)) {
+    uint32_t lo4[4], hi4[4];
+    swar_transpose4(Pi[0], Pi[1], Pi[2], Pi[3], lo4);
+    swar_transpose4(Pi[4], Pi[5], Pi[6], Pi[7], hi4);
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+      x[r] = ((uint64_t)hi4[r] << 32) | lo4[r];
+    }
+  };
+  // The last word is peeled: there the first member's tile is complete and
+  // leaves, and the others fill the tile from their earlier words and the
+  // last word's compares -- a member holds kNsHeldMax - 1 words, not all
+  uint64_t held[kNlWS - 1][kNsHeldMax - 1][4];
+  uint32_t P[kNlWS][8];
+  const uint32_t wl = Wm - 1;
+#pragma unroll 1
+  for (uint32_t w = 0; w < wl; ++w) {
+    word(w, P);
+#pragma unroll
+    for (uint32_t i = 0; i < kNlWS; ++i) {
+      if (i < cnt) {
+        uint64_t x[4];
+        words4(P[i], x);
+        if (i == 0) {
+#pragma unroll
+          for (uint32_t r = 0; r < 4; ++r) {
+            tile[(4 * lane + r) * Wm + w] = x[r];
+          }
+        } else {
+#pragma unroll
+          for (uint32_t ww = 0; ww + 1 < kNsHeldMax; ++ww) {
+            if (ww == w) { // static register indices
+#pragma unroll
+              for (uint32_t r = 0; r < 4; ++r) {
+                held[i ? i - 1 : 0][ww][r] = x[r];
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+  word(wl, P);
+#pragma unroll
+  for (uint32_t i = 0; i < kNlWS; ++i) {
+    if (i < cnt) {
+      uint8_t* row = a.nhb + __builtin_amdgcn_readfirstlane((uint32_t)mem[i].nhb_off) +
+                     ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(mem[i].nhb_off >> 32)) << 32);
+      if (i > 0) {
+        // the tile's last reads are done before its next fill
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (uint32_t ww = 0; ww + 1 < kNsHeldMax; ++ww) {
+          if (ww < wl) {
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r) {
+              tile[(4 * lane + r) * Wm + ww] = held[i ? i - 1 : 0][ww][r];
+            }
+          }
+        }
+      }
+      uint64_t x[4];
+      words4(P[i], x);
+#pragma unroll
+      for (uint32_t r = 0; r < 4; ++r) {
+        tile[(4 * lane + r) * Wm + wl] = x[r];
+      }
+      nl_tile_flush(row, vbase, a.V, Wm, tile, lane); // every lane
+      if (active && a.dist_w) {
+        nl_dist_from_levels(a, qs[i], v0, ls[i]);
+      }
+    }
+  }
+}
+
+// One block per (item, chunk), item-major; the wide groups come first (the
+// longest blocks), then the group items spread evenly among the solo items,
+// so VALU-heavy solo blocks and store-heavy group blocks are resident
+// together.  waves_per_eu(6): the LDS tiles allow 6 waves per SIMD, so the
+// bodies may use the 80 VGPRs that go with it (nl_v2_wide_group does) and no
+// more.  A BFS deeper than 254 levels leaves
 // everything to spf_nh_levels_swar_kernel.
 // TRITS: the instance with the 2-bit neighbour-row path compiled in
 // (OPENR_NL_TRIT=1); the default instance carries the byte path alone
 template <uint32_t T, bool TRITS>
-__global__ __launch_bounds__(T) void spf_nh_levels_v2_kernel(NhLevelsArgs a, NlV2Args v) {
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) void
+spf_nh_levels_v2_kernel(NhLevelsArgs a, NlV2Args v) {
   // per wave: the 256-node mask tile of a wide solo source (nl_store_wide)
   __shared__ uint64_t tiles[T / 64][256 * kNsHeldMax];
   uint64_t* tile = tiles[threadIdx.x >> 6];
@@ -4719,6 +4933,18 @@ __global__ __launch_bounds__(T) void spf_nh_levels_v2_kernel(NhLevelsArgs a, NlV
   const uint32_t nch = (a.V + 4 * T - 1) / (4 * T);
   uint32_t k = blockIdx.x / nch;
   const uint32_t c = blockIdx.x - k * nch;
+  // the wide groups first: their blocks are the longest
+  if constexpr (!TRITS) {
+    if (k < v.nwide) {
+      if (sh) {
+        nl_v2_wide_group<T, true>(a, v, k, c, tile, rs);
+      } else {
+        nl_v2_wide_group<T, false>(a, v, k, c, tile, rs);
+      }
+      return;
+    }
+    k -= v.nwide;
+  }
   // Bresenham spread of the nsub group items over the items
   const uint32_t per = v.nsolo + v.nsub;
   const uint32_t gi = (uint32_t)((uint64_t)k * v.nsub / per);
@@ -9699,10 +9925,11 @@ struct DevEvent {
 // The v2 next-hop pass's tables (spf_nh_levels_v2_kernel): every source with
 // at most kNsHeldMax mask words is a solo item or a member of a group of
 // sources with the same short distinct-neighbour list (<= kNlGN neighbours,
-// one word); entries list each solo source's / group's neighbours as
-// (level-row index, node).
+// one word) or of a wide shared group (NlWide, below); entries list each
+// solo source's / group's neighbours as (level-row index, node).
 int build_nl_v2(spf_query* q, const uint32_t* sources, const std::vector<int32_t>& row_of) {
   const spf_graph* g = q->g;
+  const auto t_build = std::chrono::steady_clock::now();
   std::vector<NlSolo> solo;
   std::vector<NlSub> subs;
   std::vector<NlMem> mem;
@@ -9761,6 +9988,134 @@ int build_nl_v2(spf_query* q, const uint32_t* sources, const std::vector<int32_t
       subs.push_back(sb);
     }
   }
+  // Wide shared groups (the default; OPENR_NL_WIDE_GROUPS=0: none; not with the 2-bit rows):
+  // among the would-be solo sources with whole-word mask rows, those whose
+  // lists have one length and agree on at least half of their 8-entry
+  // blocks.  Found by hashing blocks (position and ids), O(sum of degrees):
+  // a source is bucketed by its rarest block that some other source has too
+  // (the fabric: an FSW's pod, 8 sources, before its plane, 173), buckets
+  // are cut into groups of kNlWS in source order, and only a group's own
+  // members are compared id by id.
+  std::vector<NlWide> wide;
+  uint32_t wide_members = 0, wide_shared = 0, wide_private = 0;
+  if (env_flag("OPENR_NL_WIDE_GROUPS", 1) && !env_flag("OPENR_NL_TRIT", 0)) {
+    auto deg = [&](uint32_t i) { return g->nbr_off[sources[i] + 1] - g->nbr_off[sources[i]]; };
+    auto blk_hash = [&](uint32_t i, uint32_t b) {
+      const uint32_t s = sources[i], n = deg(i);
+      uint64_t h = 0x9E3779B97F4A7C15ull * (b + 1);
+      for (uint32_t j = 8 * b; j < std::min(n, 8 * b + 8); ++j) {
+        h = (h ^ g->nbrs[g->nbr_off[s] + j]) * 0x100000001B3ull;
+        h ^= h >> 29;
+      }
+      return h;
+    };
+    // every candidate's block hashes, computed once (hs[hoff[c] + b])
+    std::vector<uint32_t> cand, hoff;
+    std::vector<uint64_t> hs;
+    for (const uint32_t i : soloQ) {
+      if (q->nh_b[i] == 8 * q->nh_w[i] && deg(i) > 0) {
+        cand.push_back(i);
+        hoff.push_back((uint32_t)hs.size());
+        for (uint32_t b = 0; b < (deg(i) + 7) / 8; ++b) {
+          hs.push_back(blk_hash(i, b));
+        }
+      }
+    }
+    hoff.push_back((uint32_t)hs.size());
+    std::unordered_map<uint64_t, uint32_t> pop;
+    pop.reserve(hs.size());
+    for (const uint64_t h : hs) {
+      ++pop[h];
+    }
+    std::unordered_map<uint64_t, size_t> bucket_of;
+    std::vector<std::vector<uint32_t>> buckets; // in first-member order
+    for (size_t c = 0; c < cand.size(); ++c) {
+      const uint32_t i = cand[c];
+      uint64_t anchor = 0;
+      uint32_t best = 0;
+      for (uint32_t x = hoff[c]; x < hoff[c + 1]; ++x) {
+        const uint32_t p = pop.find(hs[x])->second;
+        if (p >= 2 && (best == 0 || p < best)) {
+          best = p;
+          anchor = hs[x];
+        }
+      }
+      if (best == 0) {
+        continue;
+      }
+      const uint64_t key = (anchor ^ ((uint64_t)deg(i) << 40)) * 0x100000001B3ull + q->nh_w[i];
+      auto [it, fresh] = bucket_of.try_emplace(key, buckets.size());
+      if (fresh) {
+        buckets.emplace_back();
+      }
+      buckets[it->second].push_back(i);
+    }
+    std::vector<char> taken(q->nq, 0);
+    for (const auto& bk : buckets) {
+      for (size_t m = 0; m + 1 < bk.size(); m += kNlWS) {
+        const uint32_t cnt = (uint32_t)std::min<size_t>(kNlWS, bk.size() - m);
+        if (cnt < 2) {
+          break; // a one-member remainder stays solo
+        }
+        const uint32_t i0 = bk[m], n = deg(i0), nblk = (n + 7) / 8;
+        const uint32_t* l0 = g->nbrs.data() + g->nbr_off[sources[i0]];
+        bool same = true;
+        uint32_t shmask = nblk >= 32 ? 0u : (1u << nblk) - 1u;
+        for (uint32_t x = 1; x < cnt && same; ++x) {
+          const uint32_t i = bk[m + x];
+          same = deg(i) == n && q->nh_w[i] == q->nh_w[i0] && q->nh_b[i] == q->nh_b[i0];
+          const uint32_t* l = g->nbrs.data() + g->nbr_off[sources[i]];
+          for (uint32_t j = 0; j < n && same; ++j) {
+            if (l[j] != l0[j]) {
+              shmask &= ~(1u << (j / 8));
+            }
+          }
+        }
+        uint32_t nsh = 0;
+        for (uint32_t b = 0; b < nblk; ++b) {
+          nsh += (shmask >> b) & 1u;
+        }
+        if (!same || 2 * nsh < nblk) {
+          continue; // its members stay solo
+        }
+        auto addBlocks = [&](uint32_t i, bool shared) {
+          const uint32_t lo = (uint32_t)ent.size();
+          const uint32_t* l = g->nbrs.data() + g->nbr_off[sources[i]];
+          for (uint32_t b = 0; b < nblk; ++b) {
+            if ((((shmask >> b) & 1u) != 0) == shared) {
+              for (uint32_t j = 8 * b; j < 8 * b + 8; ++j) { // a partial block: zero padding
+                ent.push_back(j < n ? NlEnt{(uint32_t)row_of[l[j]], l[j]} : NlEnt{0u, 0u});
+              }
+            }
+          }
+          return lo;
+        };
+        NlWide wd{};
+        wd.m0 = (uint32_t)mem.size();
+        wd.cnt = cnt;
+        wd.n = n;
+        wd.lo = addBlocks(i0, true);
+        wd.B = q->nh_b[i0];
+        wd.Wm = q->nh_w[i0];
+        wd.shmask = shmask;
+        for (uint32_t x = 0; x < cnt; ++x) {
+          const uint32_t i = bk[m + x];
+          mem.push_back(NlMem{i, addBlocks(i, false), q->nhb_off[i]});
+          taken[i] = 1;
+        }
+        wide.push_back(wd);
+        wide_members += cnt;
+        wide_shared += nsh;
+        wide_private += nblk - nsh;
+      }
+    }
+    soloQ.erase(std::remove_if(soloQ.begin(), soloQ.end(), [&](uint32_t i) { return taken[i] != 0; }),
+                soloQ.end());
+    // heavy groups first
+    std::stable_sort(wide.begin(), wide.end(), [](const NlWide& x, const NlWide& y) {
+      return (uint64_t)x.n * x.cnt > (uint64_t)y.n * y.cnt;
+    });
+  }
   // heavy solo sources first: their blocks are the longest
   std::stable_sort(soloQ.begin(), soloQ.end(), [&](uint32_t x, uint32_t y) {
     const uint32_t sx = sources[x], sy = sources[y];
@@ -9778,7 +10133,7 @@ int build_nl_v2(spf_query* q, const uint32_t* sources, const std::vector<int32_t
     solo.push_back(so);
   }
   const uint32_t nch = (g->V + 1023) / 1024;
-  if ((uint64_t)(solo.size() + subs.size()) * nch > 0x7FFFFFFFull) {
+  if ((uint64_t)(wide.size() + solo.size() + subs.size()) * nch > 0x7FFFFFFFull) {
     return SPF_OK; // the held kernel's own limit check reports it
   }
   const uint64_t lvl_bytes = (uint64_t)q->nrows * q->Vp8;
@@ -9793,8 +10148,10 @@ int build_nl_v2(spf_query* q, const uint32_t* sources, const std::vector<int32_t
   const size_t o_solo = 0, o_sub = al(o_solo + solo.size() * sizeof(NlSolo)),
                o_mem = al(o_sub + subs.size() * sizeof(NlSub)),
                o_ent = al(o_mem + mem.size() * sizeof(NlMem)),
-               total = al(o_ent + ent.size() * sizeof(NlEnt));
+               o_wide = al(o_ent + ent.size() * sizeof(NlEnt)),
+               total = al(o_wide + wide.size() * sizeof(NlWide));
   std::vector<uint8_t> host(total, 0);
+  std::memcpy(host.data() + o_wide, wide.data(), wide.size() * sizeof(NlWide));
   std::memcpy(host.data() + o_solo, solo.data(), solo.size() * sizeof(NlSolo));
   std::memcpy(host.data() + o_sub, subs.data(), subs.size() * sizeof(NlSub));
   std::memcpy(host.data() + o_mem, mem.data(), mem.size() * sizeof(NlMem));
@@ -9810,6 +10167,16 @@ int build_nl_v2(spf_query* q, const uint32_t* sources, const std::vector<int32_t
   q->v2.ent = reinterpret_cast<const NlEnt*>(b + o_ent);
   q->v2.nsolo = (uint32_t)solo.size();
   q->v2.nsub = (uint32_t)subs.size();
+  q->v2.wide = reinterpret_cast<const NlWide*>(b + o_wide);
+  q->v2.nwide = (uint32_t)wide.size();
+  if (env_flag("OPENR_SPF_CREATE_TIMING", 0)) {
+    std::fprintf(stderr,
+                 "[build_nl_v2] solo=%zu group=%zu wide=%zu wide_members=%u wide_shared_blocks=%u "
+                 "wide_private_blocks=%u %.3f ms\n",
+                 solo.size(), subs.size(), wide.size(), wide_members, wide_shared, wide_private,
+                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build)
+                     .count());
+  }
   q->v2.lvl_bytes = (uint32_t)lvl_bytes;
   q->v2.shallow = env_flag("OPENR_NL_SHALLOW", 1) ? 1u : 0u;
   // 2-bit neighbour rows (OPENR_NL_TRIT=1, opt-in): exact when every
@@ -13006,7 +13373,8 @@ int launch_nh_levels(spf_query* q, bool unit) {
     }
     if (q->has_v2 && q->v2_gen == g->nbr_gen) {
       // v2: solo items and shared-neighbour groups (spf_nh_levels_v2_kernel)
-      const uint64_t vblocks = (uint64_t)(q->v2.nsolo + q->v2.nsub) * ((g->V + 1023) / 1024);
+      const uint64_t vblocks =
+          (uint64_t)(q->v2.nwide + q->v2.nsolo + q->v2.nsub) * ((g->V + 1023) / 1024);
       if (vblocks && q->v2.trit) {
         SPF_LAUNCH((spf_nh_levels_v2_kernel<256, true>), dim3((uint32_t)vblocks), dim3(256), 0,
                            g->stream, a, q->v2);
