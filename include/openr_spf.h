@@ -137,6 +137,11 @@ int spf_graph_patch_metrics(
 int spf_graph_set_edges(
     spf_graph* g, uint32_t n, const uint32_t* edge_idx, const uint8_t* up,
     const uint64_t* metric);
+/* Which half-edges are up: up[i] = 0 iff half-edge first + i was taken down by
+ * spf_graph_set_edges and not brought back (all ones on a graph that call never
+ * changed, and after spf_graph_update).  Host only, no device work.
+ * SPF_E_INVALID when [first, first + n) is no range of the graph's half-edges. */
+int spf_graph_edge_up(const spf_graph* g, uint32_t first, uint32_t n, uint8_t* up);
 /* Rebuild the graph in place from a new CSR of the same node set (a link
  * added or removed: LinkState::updateAdjacencyDatabase's structural changes,
  * LinkState.cpp:421-434 / :564-717) without a new handle: same device and
@@ -529,7 +534,9 @@ typedef struct spf_route_diff_map {
   const uint32_t* link_off;  /* [newer rows + 1]: offsets into link_of */
   const uint32_t* link_of;   /* per newer row, per up link in CSR order: the older row's bit
                                 position, or NONE; injective within a row.  A row's segment is
-                                its link count long, or empty: identity for that row */
+                                its link count long, or empty: identity for that row (the
+                                rows then have equal link counts; a newer row without links
+                                has no route in any cell and goes with any older row) */
   const uint32_t* dirty_off; /* [newer P + 1]: offsets into dirty_ann */
   const uint32_t* dirty_ann; /* newer node ids: announcers of the column whose prefix entry
                                 changed (a route whose best is one of them is an update).
@@ -650,12 +657,21 @@ int spf_route_table_patch_columns_sel(
 int spf_route_table_patch_elapsed_ms(spf_route_table* t, float* ms);
 
 /* A topology change that keeps the CSR layout (metrics patched with
- * spf_graph_patch_metrics, transit bits with spf_graph_set_transit), in place:
+ * spf_graph_patch_metrics, transit bits with spf_graph_set_transit, links taken
+ * down or brought back with spf_graph_set_edges), in place:
  * `q` is an all-rows query over the SAME graph as the table's, with the same
  * sources in the same order, SPF_F_NEXTHOPS, no unit metric, no ignore lists,
  * 32-bit rows, and it has run since the graph changed.  It may be the table's
  * own query re-run, or a new one (the planner fixes a query's plan at creation,
  * so a metric change that ends or starts a uniform metric needs a new one).
+ * After spf_graph_set_edges it must be a NEW query, created after that call:
+ * the next-hop mask bits follow the distinct-neighbour lists, which the call
+ * rebuilds (the mask widths may differ from the table's old query; an
+ * SPF_RT_LFA table still needs every source within 256 neighbours, else
+ * SPF_E_UNSUPPORTED).  The cells do not move: a link bit and a link metric are
+ * indexed by CSR position, a down half-edge keeps its position, never has a
+ * bit, and has link metric UINT32_MAX; spf_route_table_link_words and the
+ * link-metric row length stay those of the CSR row, down slots included.
  * spf_route_refresh_kernel recomputes every cell of the listed rows from q's
  * rows and masks and compares each with the cell it replaces in the same pass.
  * After the call every cell of a listed row is bit-equal to the cell of a table

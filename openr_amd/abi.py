@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "spf_graph_set_transit",
     "spf_graph_patch_metrics",
     "spf_graph_set_edges",
+    "spf_graph_edge_up",
     "spf_graph_set_stream",
     "spf_graph_get_stream",
     "spf_graph_needs_exact",
@@ -383,6 +384,7 @@ def load():
         "spf_graph_set_transit": (C.c_int, [vp, C.POINTER(C.c_uint8)]),
         "spf_graph_patch_metrics": (C.c_int, [vp, u32, pu32, pu64]),
         "spf_graph_set_edges": (C.c_int, [vp, u32, pu32, C.POINTER(C.c_uint8), pu64]),
+        "spf_graph_edge_up": (C.c_int, [vp, u32, u32, C.POINTER(C.c_uint8)]),
         "spf_graph_set_stream": (C.c_int, [vp, vp]),
         "spf_graph_get_stream": (vp, [vp]),
         "spf_graph_needs_exact": (C.c_int, [vp]),
@@ -667,6 +669,15 @@ class Graph:
         m = np.ascontiguousarray(metrics, dtype=np.uint64)
         _check(load().spf_graph_set_edges(self.h, len(e), _p(e, C.c_uint32), _p(u, C.c_uint8),
                                           _p(m, C.c_uint64)), "set_edges")
+
+    def edge_up(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """uint8 [n]: 0 where half-edge first + i is down (spf_graph_edge_up);
+        by default every half-edge of the graph."""
+        if n is None:
+            n = len(self.csr.col) - first
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        _check(load().spf_graph_edge_up(self.h, first, n, _p(out, C.c_uint8)), "edge_up")
+        return out[:n]
 
     def patch_metrics(self, edges, metrics):
         """Metrics of existing half-edges, in place (spf_graph_patch_metrics)."""

@@ -395,7 +395,8 @@ void AllNodesRouteTable::createAndRunTable(
 AllNodesRouteTable::AllNodesRouteTable(
     const LinkState& ls, const PrefixState& ps, bool enableV4, bool computeLfa,
     const std::unordered_set<std::string>* borderNodes, bool bgpColumns, bool bgpDryRun,
-    bool bgpUseIgpMetric, size_t spareColumns, bool bgpInPlace, size_t spareSelectedColumns)
+    bool bgpUseIgpMetric, size_t spareColumns, bool bgpInPlace, size_t spareSelectedColumns,
+    bool linksInPlace)
     : area_(ls.getArea()),
       enableV4_(enableV4),
       lfa_(computeLfa),
@@ -403,6 +404,7 @@ AllNodesRouteTable::AllNodesRouteTable(
       bgpDryRun_(bgpDryRun),
       bgpIgp_(bgpUseIgpMetric),
       bgpInPlace_(bgpInPlace),
+      linksInPlace_(linksInPlace),
       spare_(spareColumns),
       spareSel_(bgpColumns && bgpUseIgpMetric ? spareSelectedColumns : 0),
       hasBorder_(borderNodes != nullptr) {
@@ -749,8 +751,10 @@ std::vector<uint32_t> AllNodesRouteTable::diff(const AllNodesRouteTable& older) 
         "AllNodesRouteTable::diff: different bgpColumns, bgpDryRun or bgpUseIgpMetric");
   }
   // spare or freed columns: unicast columns pair by prefix, a free one with none
+  // (a down half-edge has no counterpart, whatever the other table holds at
+  // its position: the maps say so)
   if (older.names_ != names_ || holes_ || older.holes_ || older.prefixes_ != prefixes_ ||
-      older.row_ != row_ || !sameOwners) {
+      older.row_ != row_ || !sameOwners || downLinks_ || older.downLinks_) {
     return diffMapped(older);
   }
   // a changed PrefixEntry of a kept announcer changes routes whose cells are
@@ -895,21 +899,29 @@ std::vector<uint32_t> AllNodesRouteTable::diffMapped(const AllNodesRouteTable& o
       }
       const uint32_t e0 = row_[i], deg = row_[i + 1] - e0;
       const uint32_t a0 = older.row_[ia], dega = older.row_[ia + 1] - a0;
+      // (a half-edge that is down, applyTopologyChanges with linksInPlace, is
+      // no link of its table: no counterpart on either side)
       bool ident = deg == dega;
       for (uint32_t j = 0; ident && j < deg; ++j) {
-        ident = same(*halfLink_[e0 + j], *older.halfLink_[a0 + j], names_[i]);
+        ident = !isDown(e0 + j) && !older.isDown(a0 + j) &&
+            same(*halfLink_[e0 + j], *older.halfLink_[a0 + j], names_[i]);
       }
       if (ident) {
         continue;
       }
       byHash.clear();
       for (uint32_t j = 0; j < dega; ++j) {
-        byHash.emplace(older.halfLink_[a0 + j]->hash, j);
+        if (!older.isDown(a0 + j)) {
+          byHash.emplace(older.halfLink_[a0 + j]->hash, j);
+        }
       }
       for (uint32_t j = 0; j < deg; ++j) {
         uint32_t t = SPF_MAP_NONE;
         const Link& l = *halfLink_[e0 + j];
         auto [lo, hi] = byHash.equal_range(l.hash);
+        if (isDown(e0 + j)) {
+          hi = lo;
+        }
         for (auto it = lo; it != hi; ++it) {
           if (same(l, *older.halfLink_[a0 + it->second], names_[i])) {
             t = it->second;
@@ -1546,7 +1558,408 @@ AllNodesRouteTable::Row AllNodesRouteTable::fetchPrevRow(uint32_t i) const {
   return r;
 }
 
+// applyTopologyChanges of a linksInPlace table: the layout check of the plain
+// form is replaced by a match of half-edges by Link identity within each row,
+// and a half-edge may change its state as well as its metric.
+std::vector<uint32_t> AllNodesRouteTable::applyLinkChanges(const LinkState& ls) {
+  const auto tp = std::chrono::steady_clock::now();
+  const char* const who = "AllNodesRouteTable::applyTopologyChanges: ";
+  // ---- every refusal, before anything is touched
+  if (hasBorder_ || bgpColumns_) {
+    throw std::invalid_argument(std::string(who) + "a table built with borderNodes or bgpColumns");
+  }
+  if (ls.getArea() != area_) {
+    throw std::invalid_argument(std::string(who) + "another area");
+  }
+  LinkState::Engine& eng = ls.engine();
+  if (eng.exact) {
+    throw std::invalid_argument(std::string(who) + "metric 0 / 64-bit sums need the exact kernel");
+  }
+  if (eng.names != names_) {
+    throw std::invalid_argument(std::string(who) + "nodes changed (build a fresh table)");
+  }
+  const uint32_t V = (uint32_t)names_.size();
+  const size_t E = col_.size();
+  {
+    std::vector<int32_t> nodeLabel(V, 0);
+    for (const auto& [node, db] : ls.getAdjacencyDatabases()) {
+      if (db.nodeLabel == 0 || !isMplsLabelValid(db.nodeLabel)) {
+        continue;
+      }
+      if (auto it = ids_.find(node); it != ids_.end()) {
+        nodeLabel[it->second] = db.nodeLabel;
+      }
+    }
+    if (nodeLabel != nodeLabel_) {
+      throw std::invalid_argument(std::string(who) +
+                                  "a node label changed (build a fresh table)");
+    }
+  }
+  // ---- the match: partner[e] = the engine's half-edge of table half-edge e
+  // (SPF_MAP_NONE: down now)
+  auto same = [](const Link& a, const Link& b, const std::string& node) {
+    return a == b && a.getArea() == b.getArea() &&
+        a.getIfaceFromNode(node) == b.getIfaceFromNode(node) &&
+        a.getNhV4FromNode(node) == b.getNhV4FromNode(node) &&
+        a.getNhV6FromNode(node) == b.getNhV6FromNode(node);
+  };
+  std::vector<uint32_t> partner(E, SPF_MAP_NONE);
+  {
+    std::unordered_multimap<size_t, uint32_t> byHash;
+    for (uint32_t i = 0; i < V; ++i) {
+      const uint32_t e0 = row_[i], deg = row_[i + 1] - e0;
+      const uint32_t f0 = eng.row[i], degf = eng.row[i + 1] - f0;
+      // (a LinkState updated in place keeps its Link objects and the order of
+      // a row that lost or gained nothing: position and pointer first)
+      bool ident = deg == degf;
+      for (uint32_t j = 0; ident && j < deg; ++j) {
+        const std::shared_ptr<Link>& now = eng.links[eng.linkId[f0 + j]];
+        ident = now == halfLink_[e0 + j] || same(*halfLink_[e0 + j], *now, names_[i]);
+      }
+      if (ident) {
+        for (uint32_t j = 0; j < deg; ++j) {
+          partner[e0 + j] = f0 + j;
+        }
+        continue;
+      }
+      if (degf > deg) {
+        throw std::invalid_argument(std::string(who) +
+                                    "a link the table does not hold (build a fresh table)");
+      }
+      byHash.clear();
+      for (uint32_t j = 0; j < deg; ++j) {
+        byHash.emplace(halfLink_[e0 + j]->hash, e0 + j);
+      }
+      for (uint32_t f = f0; f < f0 + degf; ++f) {
+        const Link& l = *eng.links[eng.linkId[f]];
+        bool found = false;
+        auto [lo, hi] = byHash.equal_range(l.hash);
+        for (auto it = lo; it != hi; ++it) {
+          if (same(*halfLink_[it->second], l, names_[i])) {
+            partner[it->second] = f;
+            byHash.erase(it); // (a link is one half-edge of the row)
+            found = true;
+            break;
+          }
+        }
+        if (!found) {
+          throw std::invalid_argument(
+              std::string(who) +
+              "a link the table does not hold, or one that returned with another "
+              "identity (build a fresh table)");
+        }
+      }
+    }
+  }
+  // ---- what changes: state and metric per half-edge
+  std::vector<uint32_t> edges, tails;     // half-edges whose state or metric changes
+  std::vector<uint8_t> ups;
+  std::vector<uint64_t> metrics;
+  size_t stateChanges = 0, metricChanges = 0;
+  for (uint32_t i = 0; i < V; ++i) {
+    for (uint32_t e = row_[i]; e < row_[i + 1]; ++e) {
+      const bool wasUp = !isDown(e), isUp = partner[e] != SPF_MAP_NONE;
+      if (isUp != (partner[rev_[e]] != SPF_MAP_NONE)) {
+        throw std::invalid_argument(std::string(who) +
+                                    "the two halves of a link would end in different states");
+      }
+      if (isUp && eng.col[partner[e]] != col_[e]) {
+        throw std::invalid_argument(std::string(who) + "a link changed its identity");
+      }
+      // (a down half-edge keeps its last metric: never relaxed, but the engine
+      // wants a positive one)
+      const uint64_t m = isUp ? eng.metric[partner[e]] : metric_[e];
+      if (wasUp == isUp && (!isUp || m == metric_[e])) {
+        continue;
+      }
+      if (m == 0 || m > 0x7FFFFFFFull) {
+        throw std::invalid_argument(std::string(who) +
+                                    "a metric outside the in-place range (0 or above 2^31 - 1)");
+      }
+      edges.push_back(e);
+      ups.push_back(isUp ? 1 : 0);
+      metrics.push_back(m);
+      stateChanges += wasUp != isUp;
+      metricChanges += wasUp && isUp;
+      if (tails.empty() || tails.back() != i) {
+        tails.push_back(i);
+      }
+    }
+  }
+  const std::vector<uint8_t> ovNew(eng.overloaded.begin(), eng.overloaded.end());
+  const bool drained = ovNew != overloaded_;
+  // ---- edge deltas: the table's up half-edges before the call against the
+  // engine's CSR now (a multiset difference per tail: the layouts need not
+  // agree).  They only choose rows: not needed when every row is listed.
+  uint32_t nd = 0;
+  std::vector<spf_edge_delta> deltas(drained ? 0 : stateChanges + 2 * metricChanges);
+  if (!deltas.empty()) {
+    std::vector<uint32_t> rowUp(V + 1, 0), colUp;
+    std::vector<uint64_t> metricUp;
+    colUp.reserve(E);
+    metricUp.reserve(E);
+    for (uint32_t i = 0; i < V; ++i) {
+      for (uint32_t e = row_[i]; e < row_[i + 1]; ++e) {
+        if (!isDown(e)) {
+          colUp.push_back(col_[e]);
+          metricUp.push_back(metric_[e]);
+        }
+      }
+      rowUp[i + 1] = (uint32_t)colUp.size();
+    }
+    spf_graph_desc da{}, db{};
+    da.num_nodes = db.num_nodes = V;
+    da.num_edges = (uint32_t)colUp.size();
+    da.row_ptr = rowUp.data();
+    da.col = colUp.data();
+    da.metric = metricUp.data();
+    da.node_overloaded = overloaded_.data();
+    db.num_edges = (uint32_t)eng.col.size();
+    db.row_ptr = eng.row.data();
+    db.col = eng.col.data();
+    db.metric = eng.metric.data();
+    db.node_overloaded = ovNew.data();
+    da.device = db.device = getSpfDevice();
+    if (int s = spf_graph_diff(&da, &db, deltas.data(), (uint32_t)deltas.size(), &nd);
+        s != SPF_OK || nd > deltas.size()) {
+      tableFailure("spf_graph_diff", s);
+    }
+  }
+  // ---- the rows: every row when an overload bit flipped, else the screen's
+  // on the resident rows (before the graph is patched), closed for LFA
+  std::vector<uint32_t> rows;
+  std::vector<uint32_t> src(V);
+  for (uint32_t i = 0; i < V; ++i) {
+    src[i] = i;
+  }
+  if (!drained && !edges.empty()) {
+    std::vector<uint8_t> affected(V, 0);
+    if (nd) {
+      void *dist = nullptr, *nh = nullptr;
+      uint32_t eb = 0;
+      uint64_t nhWords = 0;
+      if (int s = spf_query_device_rows(query_.get(), &dist, &eb, &nh, &nhWords);
+          s != SPF_OK || eb != 4) {
+        tableFailure("spf_query_device_rows", s);
+      }
+      if (int s = spf_table_screen(graph_.get(), (const uint32_t*)dist,
+                                   spf_query_row_stride(query_.get()), V, src.data(),
+                                   deltas.data(), nd, affected.data());
+          s != SPF_OK) {
+        tableFailure("spf_table_screen", s);
+      }
+    }
+    if (nd != deltas.size()) {
+      // parallel links that exchanged metrics (or states) cancel out of the
+      // multiset deltas, yet which of them is tight is a link bit of their
+      // tail's cells
+      for (const uint32_t t : tails) {
+        affected[t] = 1;
+      }
+    }
+    // (col_ holds the heads of down half-edges too: a row next to one is
+    // listed at worst once too often)
+    rows = routeRefreshRowList(affected, row_, col_, tails, lfa_);
+  }
+  std::vector<uint32_t> counts(V, 0);
+  spf_query* q = query_.get();
+  std::unique_ptr<spf_query, QueryDeleter> fresh;
+  if (drained || !edges.empty()) {
+    if (stateChanges) {
+      // every check of spf_graph_set_edges comes before its first write: a
+      // refusal (a metric the packed edge words cannot hold) still leaves the
+      // table as it was
+      if (int s = spf_graph_set_edges(graph_.get(), (uint32_t)edges.size(), edges.data(),
+                                      ups.data(), metrics.data());
+          s == SPF_E_UNSUPPORTED) {
+        throw std::invalid_argument(std::string(who) + spf_last_error_detail());
+      } else if (s != SPF_OK) {
+        tableFailure("spf_graph_set_edges", s);
+      }
+    } else if (!edges.empty()) {
+      if (int s = spf_graph_patch_metrics(graph_.get(), (uint32_t)edges.size(), edges.data(),
+                                          metrics.data());
+          s != SPF_OK) {
+        tableFailure("spf_graph_patch_metrics", s);
+      }
+    }
+    // ---- from here on a failure leaves the table unusable
+    if (drained) {
+      if (int s = spf_graph_set_transit(graph_.get(), ovNew.data()); s != SPF_OK) {
+        tableFailure("spf_graph_set_transit", s);
+      }
+    }
+    spf_query_desc qd{};
+    qd.num_queries = V;
+    qd.sources = src.data();
+    qd.flags = SPF_F_NEXTHOPS;
+    spf_query* nq = nullptr;
+    if (int s = spf_query_create(graph_.get(), &qd, &nq); s != SPF_OK) {
+      tableFailure("spf_query_create", s);
+    }
+    fresh.reset(nq);
+    if (int s = spf_query_run(nq); s != SPF_OK) {
+      tableFailure("spf_query_run", s);
+    }
+    q = nq;
+  }
+  // (nothing moved on the graph: an all-clear bitmap over the table's own query)
+  const uint32_t none = 0;
+  if (int s = spf_route_table_refresh_rows(
+          table_.get(), q, drained ? 0 : (uint32_t)rows.size(),
+          drained ? nullptr : rows.empty() ? &none : rows.data(), counts.data());
+      s != SPF_OK) {
+    tableFailure("spf_route_table_refresh_rows", s);
+  }
+  if (fresh) {
+    query_ = std::move(fresh); // (the old query goes: the table is bound to the new one)
+    if (int s = spf_query_elapsed_ms(query_.get(), &spfMs_); s != SPF_OK) {
+      tableFailure("elapsed", s);
+    }
+  } else {
+    spfMs_ = 0;
+  }
+  if (int s = spf_route_table_refresh_elapsed_ms(table_.get(), &refreshMs_); s != SPF_OK) {
+    tableFailure("spf_route_table_refresh_elapsed_ms", s);
+  }
+  refreshRows_ = drained ? V : rows.size();
+  // ---- a link that went down or came back can move `best` (the smallest
+  // REACHABLE announcer) between announcers with equal PrefixEntries: the cell
+  // changed, the route did not.  Such cells leave this call's delta.
+  suppress_.assign(V, {});
+  std::vector<uint32_t> risk; // unicast columns where two announcers share an entry
+  for (size_t c = 0; stateChanges && c < numCols(); ++c) {
+    if (!isUni(c) || isFree(c)) {
+      continue;
+    }
+    const auto& as = annsAt(c);
+    bool twin = false;
+    for (size_t x = 0; !twin && x < as.size(); ++x) {
+      for (size_t y = x + 1; !twin && y < as.size(); ++y) {
+        twin = as[x].entry == as[y].entry;
+      }
+    }
+    if (twin) {
+      risk.push_back((uint32_t)c);
+    }
+  }
+  if (!risk.empty()) {
+    std::vector<uint32_t> rr, cc;
+    std::vector<uint64_t> bits((numCols() + 63) / 64);
+    uint64_t nl = 0, nm = 0;
+    for (uint32_t i = 0; i < V; ++i) {
+      if (!counts[i]) {
+        continue;
+      }
+      if (int s = spf_route_table_changed(table_.get(), i, bits.data()); s != SPF_OK) {
+        tableFailure("spf_route_table_changed", s);
+      }
+      const uint64_t deg = row_[i + 1] - row_[i];
+      for (const uint32_t c : risk) {
+        if ((bits[c / 64] >> (c % 64)) & 1) {
+          rr.push_back(i);
+          cc.push_back(c);
+          nl += (deg + 63) / 64;
+          nm += lfa_ ? deg : 0;
+        }
+      }
+    }
+    if (!rr.empty()) {
+      struct Cells {
+        std::vector<uint32_t> metric, best, lmet;
+        std::vector<uint64_t> links;
+      };
+      auto read = [&](decltype(&spf_route_table_fetch_cells) fetch, const char* what) {
+        Cells z;
+        z.metric.resize(rr.size());
+        z.best.resize(rr.size());
+        z.links.resize(std::max<uint64_t>(nl, 1));
+        z.lmet.resize(std::max<uint64_t>(nm, 1));
+        if (int s = fetch(table_.get(), rr.size(), rr.data(), cc.data(), z.metric.data(),
+                          z.best.data(), z.links.data(), lfa_ ? z.lmet.data() : nullptr);
+            s != SPF_OK) {
+          tableFailure(what, s);
+        }
+        return z;
+      };
+      const Cells now = read(spf_route_table_fetch_cells, "spf_route_table_fetch_cells");
+      const Cells was = read(spf_route_table_fetch_cells_prev, "spf_route_table_fetch_cells_prev");
+      auto entryOf = [&](uint32_t c, uint32_t id) -> const thrift::PrefixEntry* {
+        for (const auto& a : annsAt(c)) {
+          if (a.id == id) {
+            return &a.entry;
+          }
+        }
+        return nullptr;
+      };
+      uint64_t lw = 0, lm = 0;
+      for (size_t k = 0; k < rr.size(); ++k) {
+        const uint64_t deg = row_[rr[k] + 1] - row_[rr[k]], W = (deg + 63) / 64, M = lfa_ ? deg : 0;
+        const uint64_t lw0 = lw, lm0 = lm;
+        lw += W;
+        lm += M;
+        if (was.metric[k] == 0xFFFFFFFFu || now.metric[k] == 0xFFFFFFFFu ||
+            was.best[k] == now.best[k]) {
+          continue;
+        }
+        const auto* oe = entryOf(cc[k], was.best[k]);
+        const auto* ne = entryOf(cc[k], now.best[k]);
+        if (!oe || !ne || !(*oe == *ne)) {
+          continue;
+        }
+        // (LFA: the metric word is no part of the route, see diff())
+        if ((!lfa_ && was.metric[k] != now.metric[k]) ||
+            !std::equal(now.links.begin() + lw0, now.links.begin() + lw0 + W,
+                        was.links.begin() + lw0) ||
+            !std::equal(now.lmet.begin() + lm0, now.lmet.begin() + lm0 + M,
+                        was.lmet.begin() + lm0)) {
+          continue;
+        }
+        suppress_[rr[k]].push_back(cc[k]); // (rows and columns ascending: sorted)
+        counts[rr[k]] -= 1;
+      }
+    }
+  }
+  // ---- the host's view: states, metrics, drain bits, links, adjacency labels
+  if (stateChanges && down_.empty()) {
+    down_.assign(E, 0);
+  }
+  for (size_t k = 0; k < edges.size(); ++k) {
+    metric_[edges[k]] = metrics[k];
+    if (!down_.empty()) {
+      down_[edges[k]] = !ups[k];
+    }
+  }
+  downLinks_ = (size_t)std::count(down_.begin(), down_.end(), (uint8_t)1) / 2;
+  overloaded_ = ovNew;
+  for (size_t e = 0; e < E; ++e) {
+    // (a down half-edge keeps its Link: previous cells may name it)
+    if (partner[e] != SPF_MAP_NONE) {
+      halfLink_[e] = eng.links[eng.linkId[partner[e]]];
+    }
+  }
+  prevAdjLabels_ = std::move(adjLabels_);
+  adjLabels_.clear();
+  collectAdjLabels(ls);
+  diffed_ = true;
+  mapped_ = false;
+  patchDelta_ = false;
+  topoDelta_ = true;
+  older_ = nullptr;
+  goneCols_.clear();
+  goneNew_.clear();
+  rowOf_.resize(V);
+  for (uint32_t i = 0; i < V; ++i) {
+    rowOf_[i] = i;
+  }
+  Counters::add("decision.route_table_refresh_us", usSince(tp));
+  return counts;
+}
+
 std::vector<uint32_t> AllNodesRouteTable::applyTopologyChanges(const LinkState& ls) {
+  if (linksInPlace_) {
+    return applyLinkChanges(ls);
+  }
   const auto tp = std::chrono::steady_clock::now();
   // ---- every refusal, before anything is touched
   if (hasBorder_ || bgpColumns_) {
@@ -1730,6 +2143,7 @@ std::vector<uint32_t> AllNodesRouteTable::applyTopologyChanges(const LinkState& 
     tableFailure("spf_route_table_refresh_elapsed_ms", s);
   }
   refreshRows_ = drained ? V : rows.size();
+  suppress_.assign(V, {}); // (metrics and drains cut no announcer off: `best` stays)
   // ---- the host's view: metrics, drain bits, links, adjacency labels
   metric_ = eng.metric;
   overloaded_ = ovNew;
@@ -1771,7 +2185,7 @@ std::pair<uint32_t, uint32_t> AllNodesRouteTable::changedSplit(const std::string
   }
   uint32_t uni = 0, lab = 0;
   forEachSetBit(bits.data(), bits.size(), [&](size_t p) { (isUni(p) ? uni : lab) += 1; });
-  if (patchDelta_) {
+  if (patchDelta_ || topoDelta_) {
     uni -= (uint32_t)suppress_[it->second].size();
   }
   if (!goneCols_.empty()) {
@@ -2109,7 +2523,7 @@ std::vector<DecisionRouteUpdate> AllNodesRouteTable::deltas() const {
                links.data() + lwBase[i], lmet.data() + lmBase[i],
                devSel_ ? igp.data() + k0 : nullptr)
         : Row{};
-    if (patchDelta_ && !suppress_[i].empty()) {
+    if ((patchDelta_ || topoDelta_) && !suppress_[i].empty()) {
       std::vector<uint32_t> keep;
       for (uint64_t k = k0; k < k1; ++k) {
         if (!suppressed(i, col[k])) {

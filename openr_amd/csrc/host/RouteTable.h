@@ -105,11 +105,15 @@ class AllNodesRouteTable {
   // spareSelectedColumns (with bgpUseIgpMetric, else ignored): that many empty
   // SELECTED columns after the spare columns, for BGP prefixes announced later
   // (a column's kind is fixed when the device table is created).
+  // linksInPlace: applyTopologyChanges also follows links that go down or come
+  // back (an adjacency withdrawn or announced again, a link overload bit), see
+  // there.  Off by default only because a test pins the refusal of a removed
+  // link.
   AllNodesRouteTable(
       const LinkState& ls, const PrefixState& ps, bool enableV4 = true, bool computeLfa = false,
       const std::unordered_set<std::string>* borderNodes = nullptr, bool bgpColumns = false,
       bool bgpDryRun = false, bool bgpUseIgpMetric = false, size_t spareColumns = 0,
-      bool bgpInPlace = false, size_t spareSelectedColumns = 0);
+      bool bgpInPlace = false, size_t spareSelectedColumns = 0, bool linksInPlace = false);
   ~AllNodesRouteTable();
   AllNodesRouteTable(const AllNodesRouteTable&) = delete;
   AllNodesRouteTable& operator=(const AllNodesRouteTable&) = delete;
@@ -261,7 +265,34 @@ class AllNodesRouteTable {
   // leaves the table unusable (its graph, rows and cells no longer agree).
   // Returns the changed routes per node (unicast and node-label columns), id
   // order.
+  // linksInPlace: links of the table may also be down in `ls` or be back.  The
+  // table's half-edges keep their CSR positions for its whole life; per node
+  // they are matched to the half-edges of ls.engine() by Link identity (Link ==,
+  // area, interface, v4 and v6 next-hop address from that node), within the
+  // row and not by position.  A table half-edge without a partner is down; the
+  // table keeps its Link object (previous cells may name it) until the link
+  // returns, whose new object then replaces it.  Refused as above, before
+  // anything is touched: an engine half-edge without a partner (a brand-new
+  // link, or a returning one whose identity fields differ), node names or node
+  // labels that differ, halves of one link that would end in different states,
+  // a metric spf_graph_set_edges refuses (0, above 2^31 - 1, unpackable),
+  // ls.engine().exact, borderNodes or bgpColumns tables.  The edge deltas are
+  // spf_graph_diff of the table's up half-edges before the call and the
+  // engine's CSR now; the rows are chosen as above with the tails of every
+  // half-edge whose state or metric changed; ONE spf_graph_set_edges carries
+  // every half-edge whose state changed together with the metric changes of
+  // that call (spf_graph_patch_metrics when no state changed), then
+  // spf_graph_set_transit, the new query, the refresh and the adjacency labels
+  // as above.  A down half-edge never carries a link bit; diff() with such a
+  // table on either side goes through the maps, where a down half-edge has no
+  // counterpart.  A link that goes down can cut the smallest reachable
+  // announcer of a prefix off: a cell whose `best` alone moved, between
+  // announcers with equal PrefixEntries, is no route change and is left out of
+  // the call's counts and delta (the changed cells of such columns are read
+  // back, now and previous).
   std::vector<uint32_t> applyTopologyChanges(const LinkState& ls);
+  // links of the table that are down now (linksInPlace)
+  size_t downLinks() const { return downLinks_; }
   // device time of the last applyTopologyChanges' refresh kernel (its SPF: spfMs)
   float refreshMs() const { return refreshMs_; }
   // rows the last applyTopologyChanges listed
@@ -408,6 +439,13 @@ class AllNodesRouteTable {
   size_t nbgp_{0}, nsel_{0};
   size_t devSel_{0}; // selected columns of the device table (spare ones included)
   bool bgpColumns_{false}, bgpDryRun_{false}, bgpIgp_{false}, bgpInPlace_{false};
+  // linksInPlace: down_[e] = half-edge e of the table's CSR is down (empty: none
+  // ever was); col_ keeps every half-edge's head, down ones included
+  bool linksInPlace_{false};
+  std::vector<uint8_t> down_;
+  size_t downLinks_{0};
+  bool isDown(size_t e) const { return !down_.empty() && down_[e]; }
+  std::vector<uint32_t> applyLinkChanges(const LinkState& ls);
   std::vector<uint8_t> overloaded_; // per node id, from the snapshot (scanPrefix without LinkState)
   // 0 Open/R, 1 BGP selected on the host, 2 a selected column -- by what the
   // column serves (a free column is an Open/R one)
@@ -446,11 +484,14 @@ class AllNodesRouteTable {
   float refreshMs_{0};
   size_t refreshRows_{0};
   float patchMs_{0};
-  // per node: columns of the last applyPrefixChanges whose cell changed in
-  // `best` alone, between announcers with equal PrefixEntries (no route change)
+  // per node: columns of the last applyPrefixChanges or applyTopologyChanges
+  // whose cell changed in `best` alone, between announcers with equal
+  // PrefixEntries (no route change; a link that goes down can cut the best
+  // announcer of an anycast prefix off)
   std::vector<std::vector<uint32_t>> suppress_;
   bool suppressed(uint32_t i, uint32_t c) const {
-    return patchDelta_ && std::binary_search(suppress_[i].begin(), suppress_[i].end(), c);
+    return (patchDelta_ || topoDelta_) &&
+        std::binary_search(suppress_[i].begin(), suppress_[i].end(), c);
   }
   size_t numCols() const { return prefixes_.size() + owners_.size() + spare_ + spareSel_; }
   size_t spareBase() const { return prefixes_.size() + owners_.size(); }

@@ -483,19 +483,19 @@ PYBIND11_MODULE(_openr_spf, m) {
       .def(py::init([](const AreaMapHolder& areas, const std::string& area, const PrefixState& ps,
                        bool enableV4, bool lfa, bool bgpColumns, bool bgpDryRun,
                        bool bgpUseIgpMetric, size_t spareColumns, bool bgpInPlace,
-                       size_t spareSelectedColumns,
+                       size_t spareSelectedColumns, bool linksInPlace,
                        const std::optional<std::unordered_set<std::string>>& borderNodes) {
              // (borderNodes is read by the constructor only)
              return std::make_unique<AllNodesRouteTable>(
                  areas.map.at(area), ps, enableV4, lfa, borderNodes ? &*borderNodes : nullptr,
                  bgpColumns, bgpDryRun, bgpUseIgpMetric, spareColumns, bgpInPlace,
-                 spareSelectedColumns);
+                 spareSelectedColumns, linksInPlace);
            }),
            py::arg("areas"), py::arg("area"), py::arg("prefix_state"), py::arg("enable_v4") = true,
            py::arg("lfa") = false, py::arg("bgp_columns") = false, py::arg("bgp_dry_run") = false,
            py::arg("bgp_use_igp_metric") = false, py::arg("spare_columns") = 0,
            py::arg("bgp_in_place") = false, py::arg("spare_selected_columns") = 0,
-           py::arg("border_nodes") = py::none(), py::keep_alive<1, 2>())
+           py::arg("links_in_place") = false, py::arg("border_nodes") = py::none(), py::keep_alive<1, 2>())
       .def("apply_prefix_changes",
            [](AllNodesRouteTable& t, const PrefixState& ps, const py::iterable& prefixes) {
              // prefixes: the keys updatePrefixDatabase returns, (address bytes, length)
@@ -518,6 +518,7 @@ PYBIND11_MODULE(_openr_spf, m) {
            py::arg("areas"), py::arg("area"))
       .def_property_readonly("refresh_ms", &AllNodesRouteTable::refreshMs)
       .def_property_readonly("refresh_rows", &AllNodesRouteTable::refreshRows)
+      .def_property_readonly("down_links", &AllNodesRouteTable::downLinks)
       .def_property_readonly("free_columns", &AllNodesRouteTable::freeColumns)
       .def_property_readonly("free_selected_columns", &AllNodesRouteTable::freeSelectedColumns)
       .def_property_readonly("patch_ms", &AllNodesRouteTable::patchMs)

@@ -6547,11 +6547,13 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
         const uint32_t nb = a.col[e0 + j];
         // a link is a shortest-path link iff metric(l) == d(s, nbr): keep
         // the slot only for those (others can never be selected)
+        // (nb == s: a half-edge taken down in place, spf_graph_set_edges --
+        // no link of the route, with or without LFA: never a slot)
         st_nbr[j] = nb;
         st_w[j] = a.wout[e0 + j];
-        st_slot[j] = a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
+        st_slot[j] = nb != s && a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
         if (a.lfa) {
-          st_slotall[j] = a.slot[e0 + j];
+          st_slotall[j] = nb != s ? a.slot[e0 + j] : kInf32;
           st_dns[j] = a.dist[(size_t)a.row_of[nb] * a.Vp + s];
         }
       }
@@ -6651,7 +6653,9 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
               }
               uint32_t v = ((w >> (sl & 63)) & 1ull) ? mn - d[n] : kInf32;
               const uint32_t* rn = a.dist + (size_t)a.row_of[n] * a.Vp;
-              const uint64_t lim = (uint64_t)mn + st_dns[j];
+              // (a down link, sl == kInf32: no mask word matches, v starts at
+              // kInf32, and lim = 0 lets nothing lower it)
+              const uint64_t lim = sl == kInf32 ? 0ull : (uint64_t)mn + st_dns[j];
               for (uint32_t i = lo; i < hi; ++i) {
                 const uint32_t x = a.ann[i];
                 if (d[x] == kInf32 || !in_w(i) ||
@@ -6696,7 +6700,7 @@ __global__ __launch_bounds__(256) void spf_route_table_kernel(RouteTableArgs a) 
             sl = st_slot[j];
           } else {
             const uint32_t nb = a.col[e0 + j];
-            sl = a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
+            sl = nb != s && a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
           }
           if (sl == kInf32) {
             continue;
@@ -6822,7 +6826,9 @@ __device__ __forceinline__ void rt_cell(
           }
           uint32_t v = ((w >> (sl & 63)) & 1ull) ? mn - d[n] : kInf32;
           const uint32_t* rn = a.dist + (size_t)a.row_of[n] * a.Vp;
-          const uint64_t lim = (uint64_t)mn + st_dns[j];
+          // (a down link, sl == kInf32: no mask word matches, v starts at
+          // kInf32, and lim = 0 lets nothing lower it)
+          const uint64_t lim = sl == kInf32 ? 0ull : (uint64_t)mn + st_dns[j];
           for (uint32_t i = lo; i < hi; ++i) {
             const uint32_t x = a.ann[i];
             if (d[x] == kInf32 || !in_w(i) ||
@@ -6867,7 +6873,7 @@ __device__ __forceinline__ void rt_cell(
         sl = st_slot[j];
       } else {
         const uint32_t nb = a.col[e0 + j];
-        sl = a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
+        sl = nb != s && a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
       }
       if (sl == kInf32) {
         continue;
@@ -6895,11 +6901,13 @@ __device__ __forceinline__ void rt_stage_row(
     const uint32_t nb = a.col[e0 + j];
     // a link is a shortest-path link iff metric(l) == d(s, nbr): keep
     // the slot only for those (others can never be selected)
+    // (nb == s: a half-edge taken down in place, spf_graph_set_edges -- no
+    // link of the route, with or without LFA: never a slot)
     st_nbr[j] = nb;
     st_w[j] = a.wout[e0 + j];
-    st_slot[j] = a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
+    st_slot[j] = nb != s && a.wout[e0 + j] == d[nb] ? a.slot[e0 + j] : kInf32;
     if (a.lfa) {
-      st_slotall[j] = a.slot[e0 + j];
+      st_slotall[j] = nb != s ? a.slot[e0 + j] : kInf32;
       st_dns[j] = a.dist[(size_t)a.row_of[nb] * a.Vp + s];
     }
   }
@@ -10609,7 +10617,10 @@ void free_query(spf_query* q) {
 // order) and each half-edge's slot among them (sorted unique neighbours of u
 // staged in scratch[row[u] ..], counted, then packed; node blocks on the host
 // pool).  A half-edge taken down in place (spf_graph_set_edges) is no
-// neighbour; its slot is 0 (it is never tight, so never read).
+// neighbour; its slot is 0.  The SPF and next-hop kernels never read it (a
+// down half-edge is never tight); the route kernels, whose LFA cells look at
+// every link of the row, tell a down half-edge by head == tail when they stage
+// the row and give it no slot at all (rt_stage_row).
 // (reuse: the previous CSR's row / col / nbr_off / nbrs / slot, when the
 // graph is rebuilt in place: a row whose heads are unchanged keeps its
 // distinct-neighbour list and slots, shifted to the new offsets)
@@ -11109,7 +11120,8 @@ int patch_weights_sparse(spf_graph* g, uint32_t n, const uint32_t* edge_idx, con
     uint32_t u = (uint32_t)(std::upper_bound(g->row.begin(), g->row.end(), e) - g->row.begin()) - 1;
     uint32_t best = 0xFFFFFFFFu;
     for (uint32_t f = g->row[u]; f < g->row[u + 1]; ++f) {
-      if (g->slot[f] == g->slot[e]) {
+      // (a half-edge taken down in place has slot 0 and is no link to anyone)
+      if (g->slot[f] == g->slot[e] && (g->edge_up.empty() || g->edge_up[f])) {
         best = std::min<uint32_t>(best, (uint32_t)std::min<uint64_t>(g->w64[f], 0xFFFFFFFFull));
       }
     }
@@ -11883,6 +11895,16 @@ int spf_graph_set_edges(
   pool_free(d);
   HIP_TRY(le);
   HIP_TRY(se);
+  return SPF_OK;
+}
+
+int spf_graph_edge_up(const spf_graph* g, uint32_t first, uint32_t n, uint8_t* up) {
+  if (!g || (n && !up) || first > g->E || n > g->E - first) {
+    return fail(SPF_E_INVALID, "bad half-edge range");
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    up[i] = g->edge_up.empty() ? 1 : g->edge_up[first + i];
+  }
   return SPF_OK;
 }
 
@@ -16258,7 +16280,9 @@ int spf_route_table_diff_mapped(
       }
       const uint32_t dega = older->deg[qa];
       if (hi == lo) { // identity: the bit positions must be the same links
-        if (deg != dega) {
+        // (a newer row without links has an empty segment either way and no
+        // route in any cell, so no link word of it is ever compared)
+        if (deg != dega && deg != 0) {
           return fail(SPF_E_INVALID, "identity link map over rows with different link counts");
         }
         continue;
@@ -17107,9 +17131,19 @@ int spf_route_table_refresh_rows(
     if (sa != sb) {
       return fail(SPF_E_INVALID, "the query's sources differ from the table's");
     }
-    // (same graph, same sources: the masks have the table query's widths)
-    if (q->nh_w != q0->nh_w || q->Vp != q0->Vp) {
+    if (q->Vp != q0->Vp) {
       return fail(SPF_E_INVALID, "the query's row layout differs from the table's");
+    }
+    // (same graph, same sources: the masks have the table query's widths,
+    // unless spf_graph_set_edges changed a neighbour list in between; the cells
+    // are laid out by CSR position and do not depend on them)
+    if (q->nh_w != q0->nh_w && !g->links_patched) {
+      return fail(SPF_E_INVALID, "the query's row layout differs from the table's");
+    }
+    for (uint32_t i = 0; t->lfa && i < nq; ++i) {
+      if (q->nh_w[i] > kRtMaskWords) {
+        return fail(SPF_E_UNSUPPORTED, "LFA route table: a source with more than 256 neighbours");
+      }
     }
   }
   const uint32_t nr = rows ? num_rows : nq;
