@@ -697,7 +697,8 @@ int spf_route_table_patch_elapsed_ms(spf_route_table* t, float* ms);
  * over another graph, with other sources, without next hops, with unit metric
  * or ignore lists, a row >= the table's rows or listed twice.
  * SPF_E_UNSUPPORTED: 64-bit rows; a table with selected columns (BGP columns:
- * their selection words follow the rows too).  num_rows == 0 with a non-null
+ * their selection words follow the rows too -- spf_route_table_refresh_rows_sel
+ * below takes those).  num_rows == 0 with a non-null
  * `rows` is SPF_OK: the bitmap is all clear and the binding moves.
  * Memory: the cells the call replaces are kept in a previous-cell store of the
  * listed rows' size (grow-only; with every row listed one more cell store).
@@ -719,6 +720,37 @@ int spf_route_table_refresh_elapsed_ms(spf_route_table* t, float* ms);
 int spf_route_table_fetch_cells_prev(
     spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols,
     uint32_t* metric, uint32_t* best, uint64_t* links, uint32_t* link_metrics);
+/* spf_route_table_refresh_rows for tables with selected columns
+ * (spf_route_table_create_sel): same arguments, same host-side checks (without
+ * the selected-columns refusal), same epoch, pack state, query binding and
+ * error behaviour -- on any error nothing is touched.  On a table without
+ * selected columns it IS that call (same kernel instance, same bitmap).
+ * For a selected column nothing the host handed over depends on the topology:
+ * spf_route_refresh_kernel<true> folds the column's resident candidate list
+ * with its resident pair table and candidate flags (those of create_sel or of
+ * the last _patch_columns_sel) over q's row of the node and the graph's
+ * current transit bits, then computes the cell over the winners word, as
+ * spf_route_patch_kernel<.., true> does per column.  After the call every
+ * listed row is bit-equal to a table freshly created over `q` with
+ * spf_route_table_create_sel and the table's current lists, pair tables and
+ * flags, and run: metric, best, link words, SPF_RT_LFA link metrics and the
+ * selection words (igp and winners, spf_route_table_fetch_sel).  A cell with a
+ * route before and after whose igp word differs is changed too, so the bitmap
+ * is spf_route_table_diff(before, after) of two such tables on the listed rows.
+ * spf_route_table_delta_pack / _delta_fetch_igp and _fetch_cells_igp return the
+ * new igp words; a later _patch_columns_sel or spf_route_table_run works as
+ * after _refresh_rows.  Memory: the store also keeps the listed rows' previous
+ * igp words ([listed rows][selected columns], grow-only). */
+int spf_route_table_refresh_rows_sel(
+    spf_route_table* t, spf_query* q,
+    uint32_t num_rows, const uint32_t* rows /* distinct, < nq; NULL: every row */,
+    uint32_t* changed /*[rows of t] or NULL*/);
+/* The igp words as they were before the last refresh, for any (row, column):
+ * a listed row's come from the store, the others are the resident ones;
+ * UINT32_MAX in an unselected column.  SPF_E_UNSUPPORTED on a table without
+ * selected columns; SPF_E_INVALID when no refresh is current. */
+int spf_route_table_fetch_cells_prev_igp(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* igp);
 
 /* The delta itself (getRouteDelta, Decision.cpp:47-85: the updates and
  * deletes, not their number) of every node as one record list built on the

@@ -109,6 +109,8 @@ EXPORTED_SYMBOLS = (
     "spf_route_table_refresh_rows",
     "spf_route_table_refresh_elapsed_ms",
     "spf_route_table_fetch_cells_prev",
+    "spf_route_table_refresh_rows_sel",
+    "spf_route_table_fetch_cells_prev_igp",
     "spf_cluster_unique_id",
     "spf_cluster_create_local",
     "spf_cluster_create_rank",
@@ -505,6 +507,8 @@ def load():
         "spf_route_table_refresh_elapsed_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "spf_route_table_fetch_cells_prev": (C.c_int, [vp, C.c_uint64, pu32, pu32, pu32, pu32,
                                                        pu64, pu32]),
+        "spf_route_table_refresh_rows_sel": (C.c_int, [vp, vp, u32, pu32, pu32]),
+        "spf_route_table_fetch_cells_prev_igp": (C.c_int, [vp, C.c_uint64, pu32, pu32, pu32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
@@ -1222,7 +1226,20 @@ class RouteTable:
         were before the last refresh_rows (any row, listed there or not)."""
         return self.fetch_cells(rows, cols, degs, _fn="spf_route_table_fetch_cells_prev")
 
-    def refresh_rows(self, query: "Query", rows=None) -> np.ndarray:
+    def refresh_rows_sel(self, query: "Query", rows=None) -> np.ndarray:
+        """spf_route_table_refresh_rows_sel: refresh_rows for tables with
+        selected columns (their resident candidates are folded again over the
+        new rows; fetch_cells_prev_igp reads the igp words it replaced).  On a
+        table without selected columns it is refresh_rows."""
+        return self.refresh_rows(query, rows, _fn="spf_route_table_refresh_rows_sel")
+
+    def fetch_cells_prev_igp(self, rows, cols) -> np.ndarray:
+        """spf_route_table_fetch_cells_prev_igp: fetch_cells_igp of the cells
+        as they were before the last refresh (any row, listed there or not)."""
+        return self.fetch_cells_igp(rows, cols, _fn="spf_route_table_fetch_cells_prev_igp")
+
+    def refresh_rows(self, query: "Query", rows=None,
+                     _fn="spf_route_table_refresh_rows") -> np.ndarray:
         """spf_route_table_refresh_rows: the listed rows (None: every row) are
         recomputed in place from `query` (the table's own re-run, or a new one
         over the same graph and sources), to which the table is bound from
@@ -1236,8 +1253,7 @@ class RouteTable:
             rows = np.ascontiguousarray(rows, dtype=np.uint32)
             n = len(rows)
             ptr = _p(rows if n else np.zeros(1, dtype=np.uint32), C.c_uint32)
-        _check(load().spf_route_table_refresh_rows(self.h, query.h, n, ptr, _p(out, C.c_uint32)),
-               "spf_route_table_refresh_rows")
+        _check(getattr(load(), _fn)(self.h, query.h, n, ptr, _p(out, C.c_uint32)), _fn)
         self.num_gone = 0
         return out[: self.n]
 
@@ -1300,7 +1316,7 @@ class RouteTable:
                "spf_route_table_delta_fetch_igp")
         return igp[:cells]
 
-    def fetch_cells_igp(self, rows, cols) -> np.ndarray:
+    def fetch_cells_igp(self, rows, cols, _fn="spf_route_table_fetch_cells_igp") -> np.ndarray:
         """spf_route_table_fetch_cells_igp: the igp word of the cells
         (rows[k], cols[k]).  Tables with selected columns only."""
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
@@ -1308,9 +1324,9 @@ class RouteTable:
         n = len(rows)
         assert len(cols) == n
         igp = np.zeros(max(n, 1), dtype=np.uint32)
-        _check(load().spf_route_table_fetch_cells_igp(
+        _check(getattr(load(), _fn)(
             self.h, n, _p(rows, C.c_uint32) if n else None, _p(cols, C.c_uint32) if n else None,
-            _p(igp, C.c_uint32)), "spf_route_table_fetch_cells_igp")
+            _p(igp, C.c_uint32)), _fn)
         return igp[:n]
 
 

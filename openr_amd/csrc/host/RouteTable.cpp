@@ -1558,6 +1558,161 @@ AllNodesRouteTable::Row AllNodesRouteTable::fetchPrevRow(uint32_t i) const {
   return r;
 }
 
+void AllNodesRouteTable::refuseTopologyChanges(const char* who) const {
+  if (hasBorder_) {
+    throw std::invalid_argument(std::string(who) + "a table built with borderNodes");
+  }
+  if (bgpColumns_ && !bgpInPlace_) {
+    throw std::invalid_argument(std::string(who) + "a table built with bgpColumns and without "
+                                                   "bgpInPlace");
+  }
+  if (bgpColumns_ && !bgpIgp_) {
+    // (the winners of a host-selected column depend on the drain filter and on
+    // every node reaching every announcer, and reachesAll_ would go stale)
+    throw std::invalid_argument(std::string(who) + "a table built with bgpColumns and without "
+                                                   "bgpUseIgpMetric (host-selected BGP columns)");
+  }
+}
+
+void AllNodesRouteTable::refreshListedRows(
+    spf_query* q, bool all, const std::vector<uint32_t>& rows, std::vector<uint32_t>& counts) {
+  // (nothing listed: an all-clear bitmap over the given query)
+  const uint32_t none = 0;
+  const uint32_t n = all ? 0 : (uint32_t)rows.size();
+  const uint32_t* list = all ? nullptr : rows.empty() ? &none : rows.data();
+  // a device table with selected columns: their fold runs again in the same pass
+  if (devSel_) {
+    if (int s = spf_route_table_refresh_rows_sel(table_.get(), q, n, list, counts.data());
+        s != SPF_OK) {
+      tableFailure("spf_route_table_refresh_rows_sel", s);
+    }
+    return;
+  }
+  if (int s = spf_route_table_refresh_rows(table_.get(), q, n, list, counts.data());
+      s != SPF_OK) {
+    tableFailure("spf_route_table_refresh_rows", s);
+  }
+}
+
+// A metric change moves the best candidate of a selected column often (every
+// candidate's vector carries its distance).  The device reports the cell
+// (best is a cell word); the route is the same where the old and the new best
+// candidate have equal entries AND equal loopbacks and metric (non-LFA), links,
+// link metrics and the igp word all stayed -- the rule applyPrefixChanges uses
+// for kept selected columns.
+void AllNodesRouteTable::suppressSelectedBest(std::vector<uint32_t>& counts) {
+  const uint32_t V = (uint32_t)names_.size();
+  std::vector<uint32_t> risk; // selected columns that hold such a candidate pair
+  for (size_t c = 0; devSel_ && c < numCols(); ++c) {
+    if (!isUni(c) || isFree(c) || columnKind(c) != 2) {
+      continue;
+    }
+    const auto& as = annsAt(c);
+    const auto& via = selAt(c).via;
+    bool twin = false;
+    for (size_t x = 0; !twin && x < as.size(); ++x) {
+      for (size_t y = x + 1; !twin && y < as.size(); ++y) {
+        twin = as[x].id != as[y].id && as[x].entry == as[y].entry && via[x] == via[y];
+      }
+    }
+    if (twin) {
+      risk.push_back((uint32_t)c);
+    }
+  }
+  if (risk.empty()) {
+    return;
+  }
+  std::vector<uint32_t> rr, cc;
+  std::vector<uint64_t> bits((numCols() + 63) / 64);
+  uint64_t nl = 0, nm = 0;
+  for (uint32_t i = 0; i < V; ++i) {
+    if (!counts[i]) {
+      continue;
+    }
+    if (int s = spf_route_table_changed(table_.get(), i, bits.data()); s != SPF_OK) {
+      tableFailure("spf_route_table_changed", s);
+    }
+    const uint64_t deg = row_[i + 1] - row_[i];
+    for (const uint32_t c : risk) {
+      if ((bits[c / 64] >> (c % 64)) & 1) {
+        rr.push_back(i);
+        cc.push_back(c);
+        nl += (deg + 63) / 64;
+        nm += lfa_ ? deg : 0;
+      }
+    }
+  }
+  if (rr.empty()) {
+    return;
+  }
+  struct Cells {
+    std::vector<uint32_t> metric, best, lmet, igp;
+    std::vector<uint64_t> links;
+  };
+  auto read = [&](decltype(&spf_route_table_fetch_cells) fetch,
+                  decltype(&spf_route_table_fetch_cells_igp) fetchIgp, const char* what) {
+    Cells z;
+    z.metric.resize(rr.size());
+    z.best.resize(rr.size());
+    z.igp.resize(rr.size());
+    z.links.resize(std::max<uint64_t>(nl, 1));
+    z.lmet.resize(std::max<uint64_t>(nm, 1));
+    if (int s = fetch(table_.get(), rr.size(), rr.data(), cc.data(), z.metric.data(),
+                      z.best.data(), z.links.data(), lfa_ ? z.lmet.data() : nullptr);
+        s != SPF_OK) {
+      tableFailure(what, s);
+    }
+    if (int s = fetchIgp(table_.get(), rr.size(), rr.data(), cc.data(), z.igp.data());
+        s != SPF_OK) {
+      tableFailure(what, s);
+    }
+    return z;
+  };
+  const Cells now = read(spf_route_table_fetch_cells, spf_route_table_fetch_cells_igp,
+                         "spf_route_table_fetch_cells");
+  const Cells was = read(spf_route_table_fetch_cells_prev, spf_route_table_fetch_cells_prev_igp,
+                         "spf_route_table_fetch_cells_prev");
+  uint64_t lw = 0, lm = 0;
+  std::vector<uint8_t> touched(V, 0);
+  for (size_t k = 0; k < rr.size(); ++k) {
+    const uint64_t deg = row_[rr[k] + 1] - row_[rr[k]], W = (deg + 63) / 64, M = lfa_ ? deg : 0;
+    const uint64_t lw0 = lw, lm0 = lm;
+    lw += W;
+    lm += M;
+    if (was.metric[k] == 0xFFFFFFFFu || now.metric[k] == 0xFFFFFFFFu ||
+        was.best[k] == now.best[k] || was.igp[k] != now.igp[k]) {
+      continue;
+    }
+    const auto& as = annsAt(cc[k]);
+    const auto& via = selAt(cc[k]).via;
+    size_t oi = as.size(), ni = as.size();
+    for (size_t x = 0; x < as.size(); ++x) {
+      oi = as[x].id == was.best[k] && oi == as.size() ? x : oi;
+      ni = as[x].id == now.best[k] && ni == as.size() ? x : ni;
+    }
+    if (oi == as.size() || ni == as.size() || !(as[oi].entry == as[ni].entry) ||
+        !(via[oi] == via[ni])) {
+      continue;
+    }
+    // (LFA: the metric word is no part of the route, see diff())
+    if ((!lfa_ && was.metric[k] != now.metric[k]) ||
+        !std::equal(now.links.begin() + lw0, now.links.begin() + lw0 + W,
+                    was.links.begin() + lw0) ||
+        !std::equal(now.lmet.begin() + lm0, now.lmet.begin() + lm0 + M,
+                    was.lmet.begin() + lm0)) {
+      continue;
+    }
+    suppress_[rr[k]].push_back(cc[k]);
+    counts[rr[k]] -= 1;
+    touched[rr[k]] = 1;
+  }
+  for (uint32_t i = 0; i < V; ++i) {
+    if (touched[i]) {
+      std::sort(suppress_[i].begin(), suppress_[i].end()); // (the plain rule's columns come first)
+    }
+  }
+}
+
 // applyTopologyChanges of a linksInPlace table: the layout check of the plain
 // form is replaced by a match of half-edges by Link identity within each row,
 // and a half-edge may change its state as well as its metric.
@@ -1565,9 +1720,7 @@ std::vector<uint32_t> AllNodesRouteTable::applyLinkChanges(const LinkState& ls) 
   const auto tp = std::chrono::steady_clock::now();
   const char* const who = "AllNodesRouteTable::applyTopologyChanges: ";
   // ---- every refusal, before anything is touched
-  if (hasBorder_ || bgpColumns_) {
-    throw std::invalid_argument(std::string(who) + "a table built with borderNodes or bgpColumns");
-  }
+  refuseTopologyChanges(who);
   if (ls.getArea() != area_) {
     throw std::invalid_argument(std::string(who) + "another area");
   }
@@ -1804,13 +1957,7 @@ std::vector<uint32_t> AllNodesRouteTable::applyLinkChanges(const LinkState& ls) 
     q = nq;
   }
   // (nothing moved on the graph: an all-clear bitmap over the table's own query)
-  const uint32_t none = 0;
-  if (int s = spf_route_table_refresh_rows(
-          table_.get(), q, drained ? 0 : (uint32_t)rows.size(),
-          drained ? nullptr : rows.empty() ? &none : rows.data(), counts.data());
-      s != SPF_OK) {
-    tableFailure("spf_route_table_refresh_rows", s);
-  }
+  refreshListedRows(q, drained, rows, counts);
   if (fresh) {
     query_ = std::move(fresh); // (the old query goes: the table is bound to the new one)
     if (int s = spf_query_elapsed_ms(query_.get(), &spfMs_); s != SPF_OK) {
@@ -1826,10 +1973,11 @@ std::vector<uint32_t> AllNodesRouteTable::applyLinkChanges(const LinkState& ls) 
   // ---- a link that went down or came back can move `best` (the smallest
   // REACHABLE announcer) between announcers with equal PrefixEntries: the cell
   // changed, the route did not.  Such cells leave this call's delta.
+  // (Selected columns have a rule of their own: suppressSelectedBest below.)
   suppress_.assign(V, {});
-  std::vector<uint32_t> risk; // unicast columns where two announcers share an entry
+  std::vector<uint32_t> risk; // Open/R columns where two announcers share an entry
   for (size_t c = 0; stateChanges && c < numCols(); ++c) {
-    if (!isUni(c) || isFree(c)) {
+    if (!isUni(c) || isFree(c) || columnKind(c) != 0) {
       continue;
     }
     const auto& as = annsAt(c);
@@ -1920,6 +2068,7 @@ std::vector<uint32_t> AllNodesRouteTable::applyLinkChanges(const LinkState& ls) 
       }
     }
   }
+  suppressSelectedBest(counts);
   // ---- the host's view: states, metrics, drain bits, links, adjacency labels
   if (stateChanges && down_.empty()) {
     down_.assign(E, 0);
@@ -1962,10 +2111,7 @@ std::vector<uint32_t> AllNodesRouteTable::applyTopologyChanges(const LinkState& 
   }
   const auto tp = std::chrono::steady_clock::now();
   // ---- every refusal, before anything is touched
-  if (hasBorder_ || bgpColumns_) {
-    throw std::invalid_argument(
-        "AllNodesRouteTable::applyTopologyChanges: a table built with borderNodes or bgpColumns");
-  }
+  refuseTopologyChanges("AllNodesRouteTable::applyTopologyChanges: ");
   if (ls.getArea() != area_) {
     throw std::invalid_argument("AllNodesRouteTable::applyTopologyChanges: another area");
   }
@@ -2124,13 +2270,7 @@ std::vector<uint32_t> AllNodesRouteTable::applyTopologyChanges(const LinkState& 
     q = nq;
   }
   // (nothing moved on the graph: an all-clear bitmap over the table's own query)
-  const uint32_t none = 0;
-  if (int s = spf_route_table_refresh_rows(
-          table_.get(), q, drained ? 0 : (uint32_t)rows.size(),
-          drained ? nullptr : rows.empty() ? &none : rows.data(), counts.data());
-      s != SPF_OK) {
-    tableFailure("spf_route_table_refresh_rows", s);
-  }
+  refreshListedRows(q, drained, rows, counts);
   if (fresh) {
     query_ = std::move(fresh); // (the old query goes: the table is bound to the new one)
     if (int s = spf_query_elapsed_ms(query_.get(), &spfMs_); s != SPF_OK) {
@@ -2143,7 +2283,10 @@ std::vector<uint32_t> AllNodesRouteTable::applyTopologyChanges(const LinkState& 
     tableFailure("spf_route_table_refresh_elapsed_ms", s);
   }
   refreshRows_ = drained ? V : rows.size();
-  suppress_.assign(V, {}); // (metrics and drains cut no announcer off: `best` stays)
+  // (metrics and drains cut no announcer off: `best` of an Open/R column stays;
+  // the best candidate of a selected column follows the distances)
+  suppress_.assign(V, {});
+  suppressSelectedBest(counts);
   // ---- the host's view: metrics, drain bits, links, adjacency labels
   metric_ = eng.metric;
   overloaded_ = ovNew;

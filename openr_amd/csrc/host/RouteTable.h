@@ -242,8 +242,10 @@ class AllNodesRouteTable {
   // Topology changes that keep the CSR layout, in place: link metrics and
   // node overload (drain) bits, the common churn.  `ls` is the area's
   // LinkState now.  Throws std::invalid_argument before anything is touched
-  // for a table built with borderNodes or bgpColumns (host-selected BGP
-  // columns depend on the drain filter and on reachability), ls.engine().exact,
+  // for a table built with borderNodes, with bgpColumns and without
+  // bgpInPlace, or with bgpColumns and without bgpUseIgpMetric (host-selected
+  // BGP columns depend on the drain filter and on reachability, and the cached
+  // reachability answers would go stale), ls.engine().exact,
   // another area, node names, CSR row / col / rev / link ids or Link identities
   // that differ from the table's (a link down or up, a node joined or gone:
   // those need a fresh table and the mapped diff), or a node label that
@@ -265,6 +267,20 @@ class AllNodesRouteTable {
   // leaves the table unusable (its graph, rows and cells no longer agree).
   // Returns the changed routes per node (unicast and node-label columns), id
   // order.
+  // bgpColumns && bgpUseIgpMetric && bgpInPlace (with or without linksInPlace
+  // and LFA): every BGP column of such a table is a selected column, whose
+  // candidates, pair codes and loopback flags come from PrefixState alone;
+  // reachability and the drain filter are read on the device.  The rows are
+  // chosen as above and spf_route_table_refresh_rows_sel folds the selected
+  // columns of the listed rows again in the same pass (previous igp words
+  // kept: spf_route_table_fetch_cells_prev_igp); deltas() takes igp from the
+  // pack's igp lane.  In a selected column best (its entry and loopback) and
+  // igp are part of the route and a metric change moves best often: a changed
+  // cell whose best alone moved -- the old and the new best candidate have
+  // equal entries and equal loopbacks, and metric (non-LFA), links, link
+  // metrics and igp all stayed -- is left out of the call's counts and delta,
+  // as applyPrefixChanges does for kept selected columns (the changed cells of
+  // columns that hold such a candidate pair are read back, now and previous).
   // linksInPlace: links of the table may also be down in `ls` or be back.  The
   // table's half-edges keep their CSR positions for its whole life; per node
   // they are matched to the half-edges of ls.engine() by Link identity (Link ==,
@@ -276,7 +292,8 @@ class AllNodesRouteTable {
   // link, or a returning one whose identity fields differ), node names or node
   // labels that differ, halves of one link that would end in different states,
   // a metric spf_graph_set_edges refuses (0, above 2^31 - 1, unpackable),
-  // ls.engine().exact, borderNodes or bgpColumns tables.  The edge deltas are
+  // ls.engine().exact, borderNodes tables and the bgpColumns tables named
+  // above.  The edge deltas are
   // spf_graph_diff of the table's up half-edges before the call and the
   // engine's CSR now; the rows are chosen as above with the tails of every
   // half-edge whose state or metric changed; ONE spf_graph_set_edges carries
@@ -446,6 +463,16 @@ class AllNodesRouteTable {
   size_t downLinks_{0};
   bool isDown(size_t e) const { return !down_.empty() && down_[e]; }
   std::vector<uint32_t> applyLinkChanges(const LinkState& ls);
+  // applyTopologyChanges, both forms: the refusals by how the table was built
+  // (throws std::invalid_argument), the refresh call by the kind of device
+  // table, and -- after the refresh, suppress_ assigned -- the selected
+  // columns' changed cells whose `best` alone moved onto an equal candidate
+  // (same entry, same loopback; metric, links, link metrics, igp stayed): read
+  // back now and previous, added to suppress_ and taken out of counts
+  void refuseTopologyChanges(const char* who) const;
+  void refreshListedRows(spf_query* q, bool all, const std::vector<uint32_t>& rows,
+                         std::vector<uint32_t>& counts);
+  void suppressSelectedBest(std::vector<uint32_t>& counts);
   std::vector<uint8_t> overloaded_; // per node id, from the snapshot (scanPrefix without LinkState)
   // 0 Open/R, 1 BGP selected on the host, 2 a selected column -- by what the
   // column serves (a free column is an Open/R one)

@@ -7190,7 +7190,30 @@ struct RouteRefreshArgs {
   uint32_t nrows, pw, routes_only;
 };
 
-__global__ __launch_bounds__(256) void spf_route_refresh_kernel(RouteRefreshArgs ra) {
+// The <true> instance (spf_route_table_refresh_rows_sel on a table with
+// selected columns): as in the <.., true> patch instances, the lane that owns
+// a selected column first folds the column's resident candidates (the lists,
+// pair tables and flags that create_sel or the last patch_columns_sel left)
+// over the NEW distance row and the graph's current transit bits (rt_fold),
+// then computes the cell over the winners word (rt_cell<true>): nothing the
+// host computed for a selected column depends on the topology.  The row's
+// three selection words are overwritten where they differ, the previous igp
+// word goes into the store ([nrows][S]), and a cell whose igp word differs is
+// changed too.  The <false> instance is the kernel as it was: every SEL branch
+// is compiled out (same registers, LDS and scratch).
+struct RouteRefreshSelArgs : RouteRefreshArgs {
+  const uint64_t* pair_off; // [S + 1] the resident pair tables
+  const uint16_t* pair;
+  const uint8_t* cflags;    // parallel to t.ann
+  uint32_t* sel_w;          // [nq][S] resident selection words
+  uint32_t* sel_best;
+  uint32_t* sel_igp;
+  uint32_t* p_igp;          // the store: [nrows][S] previous igp words
+};
+
+template <bool SEL = false>
+__global__ __launch_bounds__(256) void spf_route_refresh_kernel(
+    std::conditional_t<SEL, RouteRefreshSelArgs, RouteRefreshArgs> ra) {
   __shared__ uint32_t st_nbr[kRtStage];
   __shared__ uint32_t st_w[kRtStage];
   __shared__ uint32_t st_slot[kRtStage];
@@ -7222,14 +7245,25 @@ __global__ __launch_bounds__(256) void spf_route_refresh_kernel(RouteRefreshArgs
       uint32_t nm, nbest;
       uint64_t* nl = slk + (size_t)p * WL;
       uint32_t* nlm = slm ? slm + (size_t)p * deg : nullptr;
-      rt_cell<false>(a, q, p, s, d, nhq, W, NB, e0, deg, WL, staged, st_nbr, st_w, st_slot,
-                     st_slotall, st_dns, false, ~0u, kInf32,
-                     [&](uint32_t*& metric_o, uint32_t*& best_o, uint64_t*& lkp, uint32_t*& lm) {
-                       metric_o = &nm;
-                       best_o = &nbest;
-                       lkp = nl;
-                       lm = nlm;
-                     });
+      [[maybe_unused]] bool selc = false;
+      [[maybe_unused]] uint32_t wm = ~0u, sbest = kInf32, sigp = kInf32, ks = kInf32;
+      if constexpr (SEL) {
+        ks = a.sel_of[p];
+        if (ks != kInf32) {
+          selc = true;
+          const uint32_t lo = a.ann_off[p];
+          rt_fold(a, ra.pair + ra.pair_off[ks], ra.cflags, s, d, lo, a.ann_off[p + 1] - lo, wm,
+                  sbest, sigp);
+        }
+      }
+      rt_cell<SEL>(a, q, p, s, d, nhq, W, NB, e0, deg, WL, staged, st_nbr, st_w, st_slot,
+                   st_slotall, st_dns, selc, wm, sbest,
+                   [&](uint32_t*& metric_o, uint32_t*& best_o, uint64_t*& lkp, uint32_t*& lm) {
+                     metric_o = &nm;
+                     best_o = &nbest;
+                     lkp = nl;
+                     lm = nlm;
+                   });
       const size_t o = (size_t)q * a.P + p;
       uint64_t* ol = lk + (size_t)p * WL;
       uint32_t* olm = slm ? a.lmet_out + a.lm_off[q] + (size_t)p * deg : nullptr;
@@ -7238,6 +7272,24 @@ __global__ __launch_bounds__(256) void spf_route_refresh_kernel(RouteRefreshArgs
         ch = om != nm;
       } else {
         ch = (om != nm && !ra.routes_only) || ob != nbest;
+      }
+      if constexpr (SEL) {
+        if (selc) {
+          const size_t os = (size_t)q * a.S + ks;
+          const uint32_t oigp = ra.sel_igp[os];
+          // (igp is kInf32 exactly where the metric is: with one side routeless ch is set)
+          ch = ch || oigp != sigp;
+          ra.p_igp[(size_t)r * a.S + ks] = oigp;
+          if (oigp != sigp) {
+            ra.sel_igp[os] = sigp;
+          }
+          if (ra.sel_w[os] != wm) {
+            ra.sel_w[os] = wm;
+          }
+          if (ra.sel_best[os] != sbest) {
+            ra.sel_best[os] = sbest;
+          }
+        }
       }
       ra.p_metric[(size_t)r * a.P + p] = om;
       ra.p_best[(size_t)r * a.P + p] = ob;
@@ -15646,8 +15698,9 @@ struct spf_route_table {
   // = the cells of listed row rf_rows[r] before the refresh, laid out like the
   // row), the slot of every row in it (kInf32: not listed, its resident cells
   // are its previous ones) and the entries' offsets; evr0 .. evr1 time the
-  // kernel.  rf_valid: a refresh is current (no run or patch since)
-  DevBuf<uint32_t> d_rf_rows, d_rf_metric, d_rf_best, d_rf_lmet;
+  // kernel.  rf_valid: a refresh is current (no run or patch since).
+  // d_rf_igp (spf_route_table_refresh_rows_sel): entry r's [S] previous igp words
+  DevBuf<uint32_t> d_rf_rows, d_rf_metric, d_rf_best, d_rf_lmet, d_rf_igp;
   DevBuf<uint64_t> d_rf_links, d_rf_lk_off, d_rf_lm_off;
   std::vector<uint32_t> rf_rows, rf_slot;
   std::vector<uint64_t> rf_lk_off, rf_lm_off; // [rf_rows.size() + 1]
@@ -16980,7 +17033,8 @@ int spf_route_table_delta_fetch_igp(spf_route_table* t, uint32_t* igp) {
 namespace {
 // spf_route_table_fetch_cells (igp null) and _fetch_cells_igp (igp alone).
 // `prev`: the cells come from the previous-cell store of the last refresh and
-// rows[] holds store entries (spf_route_table_fetch_cells_prev).
+// rows[] holds store entries (spf_route_table_fetch_cells_prev, and with igp
+// _fetch_cells_prev_igp: the store's [entries][S] igp words).
 int fetch_cells_impl(
     spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* metric,
     uint32_t* best, uint64_t* links, uint32_t* link_metrics, uint32_t* igp_out, bool igp,
@@ -17046,7 +17100,7 @@ int fetch_cells_impl(
              prev ? t->d_rf_best.p : t->d_best.p, prev ? t->d_rf_links.p : t->d_links.p,
              prev ? t->d_rf_lk_off.p : t->d_lk_off.p,
              igp ? nullptr : t->d_gc_out.p, t->d_gc_out + n, t->d_gc_links, t->d_sel_of,
-             t->d_sel_igp, t->S, igp ? t->d_gc_out + 2 * n : nullptr);
+             prev ? t->d_rf_igp.p : t->d_sel_igp.p, t->S, igp ? t->d_gc_out + 2 * n : nullptr);
   HIP_TRY(hipGetLastError());
   if (igp) {
     HIP_TRY(hipMemcpyAsync(igp_out, t->d_gc_out + 2 * n, n * 4, hipMemcpyDeviceToHost,
@@ -17090,9 +17144,14 @@ int spf_route_table_fetch_cells_igp(
   return fetch_cells_impl(t, n, rows, cols, nullptr, nullptr, nullptr, nullptr, igp, true);
 }
 
-int spf_route_table_refresh_rows(
-    spf_route_table* t, spf_query* q, uint32_t num_rows, const uint32_t* rows, uint32_t* changed) {
-  SPF_ABI_RANGE("spf_route_table_refresh_rows");
+} // extern "C"
+
+namespace {
+// spf_route_table_refresh_rows (sel false: a table with selected columns is
+// refused) and _refresh_rows_sel
+int route_refresh_apply(
+    spf_route_table* t, spf_query* q, uint32_t num_rows, const uint32_t* rows, uint32_t* changed,
+    bool sel) {
   if (!t || !q) {
     return fail(SPF_E_INVALID, "null argument");
   }
@@ -17113,11 +17172,11 @@ int spf_route_table_refresh_rows(
   if (rows64(q)) {
     return fail(SPF_E_UNSUPPORTED, "64-bit distance rows");
   }
-  if (t->S) {
+  if (t->S && !sel) {
     return fail(SPF_E_UNSUPPORTED, "a table with selected columns (their selection words follow "
-                                   "the rows too: recreate the table)");
+                                   "the rows too: spf_route_table_refresh_rows_sel)");
   }
-  const uint32_t nq = q0->nq, P = t->P, pw = (P + 63) / 64;
+  const uint32_t nq = q0->nq, P = t->P, pw = (P + 63) / 64, S = t->S;
   HIP_TRY(hipSetDevice(g->device));
   if (q != q0) {
     if (q->nq != nq) {
@@ -17175,7 +17234,8 @@ int spf_route_table_refresh_rows(
     if (t->d_rf_metric.reserve((size_t)nr * P) != hipSuccess ||
         t->d_rf_best.reserve((size_t)nr * P) != hipSuccess ||
         t->d_rf_links.reserve((size_t)lk[nr]) != hipSuccess ||
-        t->d_rf_lmet.reserve((size_t)lm[nr]) != hipSuccess) {
+        t->d_rf_lmet.reserve((size_t)lm[nr]) != hipSuccess ||
+        t->d_rf_igp.reserve((size_t)nr * S) != hipSuccess) {
       return fail(SPF_E_NOMEM, "previous-cell store");
     }
   }
@@ -17216,7 +17276,7 @@ int spf_route_table_refresh_rows(
   }
   HIP_TRY(hipEventRecord(t->evr0, g->stream));
   if (nr && P) {
-    RouteRefreshArgs ra{};
+    RouteRefreshSelArgs ra{};
     RouteTableArgs& a = ra.t;
     a.row = g->d_row;
     a.col = g->d_col;
@@ -17254,7 +17314,22 @@ int spf_route_table_refresh_rows(
     ra.nrows = nr;
     ra.pw = pw;
     ra.routes_only = t->diff_routes ? 1u : 0u;
-    SPF_LAUNCH(spf_route_refresh_kernel, dim3(nr), dim3(256), 0, g->stream, ra);
+    if (S) {
+      a.sel_of = t->d_sel_of;
+      a.S = S;
+      ra.pair_off = t->d_pair_off;
+      ra.pair = t->d_pair;
+      ra.cflags = t->d_cflags;
+      ra.sel_w = t->d_sel_w;
+      ra.sel_best = t->d_sel_best;
+      ra.sel_igp = t->d_sel_igp;
+      ra.p_igp = t->d_rf_igp;
+      auto* kern = spf_route_refresh_kernel<true>;
+      SPF_LAUNCH_AS("spf_route_refresh_kernel", kern, dim3(nr), dim3(256), 0, g->stream, ra);
+    } else {
+      SPF_LAUNCH_AS("spf_route_refresh_kernel", spf_route_refresh_kernel<false>, dim3(nr),
+                    dim3(256), 0, g->stream, static_cast<const RouteRefreshArgs&>(ra));
+    }
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(t->evr1, g->stream));
@@ -17264,6 +17339,21 @@ int spf_route_table_refresh_rows(
   HIP_TRY(hipStreamSynchronize(g->stream));
   t->rf_valid = true;
   return SPF_OK;
+}
+} // namespace
+
+extern "C" {
+
+int spf_route_table_refresh_rows(
+    spf_route_table* t, spf_query* q, uint32_t num_rows, const uint32_t* rows, uint32_t* changed) {
+  SPF_ABI_RANGE("spf_route_table_refresh_rows");
+  return route_refresh_apply(t, q, num_rows, rows, changed, false);
+}
+
+int spf_route_table_refresh_rows_sel(
+    spf_route_table* t, spf_query* q, uint32_t num_rows, const uint32_t* rows, uint32_t* changed) {
+  SPF_ABI_RANGE("spf_route_table_refresh_rows_sel");
+  return route_refresh_apply(t, q, num_rows, rows, changed, true);
 }
 
 int spf_route_table_refresh_elapsed_ms(spf_route_table* t, float* ms) {
@@ -17342,6 +17432,56 @@ int spf_route_table_fetch_cells_prev(
         std::copy_n(plm.begin() + am, t->deg[rows[k]], link_metrics + mpos[k]);
         am += t->deg[rows[k]];
       }
+    }
+  }
+  return SPF_OK;
+}
+
+int spf_route_table_fetch_cells_prev_igp(
+    spf_route_table* t, uint64_t n, const uint32_t* rows, const uint32_t* cols, uint32_t* igp) {
+  SPF_ABI_RANGE("spf_route_table_fetch_cells_prev_igp");
+  if (!t) {
+    return fail(SPF_E_INVALID, "null table");
+  }
+  if (!t->S) {
+    return fail(SPF_E_UNSUPPORTED, "the table has no selected columns (no igp word)");
+  }
+  if (!t->rf_valid) {
+    return fail(SPF_E_INVALID, "no refresh is current on this table");
+  }
+  if (n == 0) {
+    return SPF_OK;
+  }
+  if (!rows || !cols || !igp) {
+    return fail(SPF_E_INVALID, "null argument");
+  }
+  // as spf_route_table_fetch_cells_prev: listed rows from the store, the others resident
+  const uint32_t nq = t->q->nq, P = t->P;
+  std::vector<uint64_t> idx[2];
+  std::vector<uint32_t> rr[2], cc[2];
+  for (uint64_t k = 0; k < n; ++k) {
+    if (rows[k] >= nq || cols[k] >= P) {
+      return fail(SPF_E_INVALID, "cell row or column out of range");
+    }
+    const uint32_t sl = t->rf_slot[rows[k]];
+    const int w = sl != kInf32;
+    idx[w].push_back(k);
+    rr[w].push_back(w ? sl : rows[k]);
+    cc[w].push_back(cols[k]);
+  }
+  for (int w = 0; w < 2; ++w) {
+    const uint64_t m = idx[w].size();
+    if (!m) {
+      continue;
+    }
+    std::vector<uint32_t> pi(m);
+    if (int st = fetch_cells_impl(t, m, rr[w].data(), cc[w].data(), nullptr, nullptr, nullptr,
+                                  nullptr, pi.data(), true, w == 1);
+        st != SPF_OK) {
+      return st;
+    }
+    for (uint64_t j = 0; j < m; ++j) {
+      igp[idx[w][j]] = pi[j];
     }
   }
   return SPF_OK;
