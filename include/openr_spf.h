@@ -166,8 +166,41 @@ int spf_graph_nbrs(const spf_graph* g, uint32_t node, uint32_t* out);
 /* ---- queries ---- */
 int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out);
 int spf_query_destroy(spf_query* q);
-/* Enqueue the batch on the graph stream (asynchronous). */
+/* Enqueue the batch on the graph stream (asynchronous).
+ *
+ * A query may be run again after the graph changed under it in place
+ * (spf_graph_set_transit, spf_graph_patch_metrics, spf_graph_set_edges).  Its
+ * plan was fixed by spf_query_create, so the run does one of two things:
+ *   - it computes exactly what a query created now over the same sources,
+ *     flags and ignore lists would compute (distances bit for bit; next-hop
+ *     sets equal, mask bits by the graph's current spf_graph_nbrs); or
+ *   - it returns SPF_E_INVALID with a detail that begins "stale query:" and
+ *     names the fact that moved, records and launches nothing, and leaves the
+ *     last run's results readable.  Destroy the query and create a new one.
+ * It never returns wrong rows.  The sub-queries a query owns (what-if
+ * baselines and first-hop rows, the zero-metric plan's wide sources) are
+ * covered by it.
+ *
+ * What a live query survives: any transit change that leaves
+ * spf_graph_needs_exact as it was; any metric patch under SPF_F_UNIT_METRIC;
+ * metric patches that keep the graph's class (weighted stays 32-bit and, where
+ * the plan reads packed edge words or LDS rows, packable and at most 4,094;
+ * uniform stays uniform at any value; the metric-0 half-edges stay the same
+ * set and the zero-metric plan keeps one nonzero value); links down and up
+ * after which every source keeps its next-hop mask width (1, 2, 4 or 8k
+ * bytes per node) and every up neighbour has a row in a batch whose next hops
+ * come from rows.
+ * What it does not: a change of spf_graph_needs_exact; a uniform metric that
+ * ends under any query created while it held (whatever its plan, unless
+ * SPF_F_UNIT_METRIC); metric 0 or a wrapping metric introduced or
+ * removed; one half of a link down alone; a mask width class crossed; a
+ * neighbour that came up without a row in the batch; SPF_F_ORDER after
+ * spf_graph_set_edges. */
 int spf_query_run(spf_query* q);
+/* 1 if spf_query_run would refuse q as stale, else 0 (also for NULL).  Host
+ * only: one integer compare while the graph is unchanged since the last
+ * call; per-source work only after spf_graph_set_edges. */
+int spf_query_stale(const spf_query* q);
 /* Wait for the last run to finish. */
 int spf_query_sync(spf_query* q);
 /* Device time of the last run's kernels (HIP events), milliseconds. */
@@ -662,8 +695,9 @@ int spf_route_table_patch_elapsed_ms(spf_route_table* t, float* ms);
  * `q` is an all-rows query over the SAME graph as the table's, with the same
  * sources in the same order, SPF_F_NEXTHOPS, no unit metric, no ignore lists,
  * 32-bit rows, and it has run since the graph changed.  It may be the table's
- * own query re-run, or a new one (the planner fixes a query's plan at creation,
- * so a metric change that ends or starts a uniform metric needs a new one).
+ * own query re-run, or a new one (the planner fixes a query's plan at creation:
+ * spf_query_run refuses a re-run the change made stale, see there -- a metric
+ * change that ends a uniform metric needs a new one).
  * After spf_graph_set_edges it must be a NEW query, created after that call:
  * the next-hop mask bits follow the distinct-neighbour lists, which the call
  * rebuilds (the mask widths may differ from the table's old query; an

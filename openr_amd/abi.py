@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "spf_query_create",
     "spf_query_destroy",
     "spf_query_run",
+    "spf_query_stale",
     "spf_query_sync",
     "spf_query_elapsed_ms",
     "spf_query_stage_ms",
@@ -395,6 +396,7 @@ def load():
         "spf_query_create": (C.c_int, [vp, C.POINTER(_QueryDesc), C.POINTER(vp)]),
         "spf_query_destroy": (C.c_int, [vp]),
         "spf_query_run": (C.c_int, [vp]),
+        "spf_query_stale": (C.c_int, [vp]),
         "spf_query_sync": (C.c_int, [vp]),
         "spf_query_elapsed_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "spf_query_screened": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -858,6 +860,11 @@ class Query:
         if sync:
             _check(lib.spf_query_sync(self.h), "spf_query_sync")
         return self
+
+    def stale(self) -> bool:
+        """True when run() would refuse this query: the graph changed in place
+        past what its plan survives (spf_query_stale; host only)."""
+        return bool(load().spf_query_stale(self.h))
 
     def sync(self):
         _check(load().spf_query_sync(self.h), "spf_query_sync")

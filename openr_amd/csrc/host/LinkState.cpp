@@ -636,7 +636,10 @@ std::vector<std::unique_ptr<SpfView>> runBatch(
   const bool reuse = cacheQuery && !ignore && eng.names.size() <= 4096;
   spf_query* q = nullptr;
   int s = SPF_OK;
-  if (reuse && eng.lastQuery && eng.lastFlags == flags && eng.lastSources == sources) {
+  // (a drain can move the graph past the kept query's plan, e.g. into 64-bit
+  // rows: spf_query_run would refuse it, so it is dropped and created anew)
+  if (reuse && eng.lastQuery && eng.lastFlags == flags && eng.lastSources == sources &&
+      !spf_query_stale(eng.lastQuery)) {
     q = eng.lastQuery;
     Counters::add("decision.spf_query_reuses", 1);
   } else {

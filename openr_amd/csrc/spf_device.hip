@@ -9609,6 +9609,16 @@ struct spf_graph {
   // spf_graph_set_edges): per-query tables built from them (the v2 next-hop
   // pass) are stale after a change
   uint64_t nbr_gen = 0;
+  // bumped by every change of the graph under its handle (spf_graph_set_transit,
+  // _patch_metrics, _set_edges, _update): spf_query_stale re-derives a query's
+  // verdict only when it moved
+  uint64_t gen = 0;
+  // hash of the sorted metric-0 half-edge list (upload_weights; the sparse
+  // patch and spf_graph_set_edges cannot change that set)
+  uint64_t zero_sig = 0;
+  // graphs with a metric 0: the one value every other metric has (0: several
+  // values, or one past 32 bits) -- the level scale of the zero-metric plan
+  uint32_t nz_uniform = 0;
 };
 
 // How a batch is computed.
@@ -9671,6 +9681,9 @@ struct spf_query {
   uint8_t* d_lvl = nullptr;
   uint32_t* d_flags = nullptr;
   uint32_t ms_par = 0; // the flag word (0 / 1) of the last MS-BFS launch
+  // the level scale of the last MS-BFS launch: spf_query_pack_levels reports
+  // the last run's rows, whatever the graph's metric is by now
+  uint32_t ms_scale = 0;
   // cooperative MS-BFS (spf_msbfs_coop_kernel): exchange buffer, barrier
   // counters, per-part flags and the error word, in one pooled block
   void* d_coop = nullptr;
@@ -9728,6 +9741,20 @@ struct spf_query {
   NlV2Args v2{};
   bool has_v2 = false;
   uint64_t v2_gen = 0;
+  // spf_query_stale: the facts of the graph this query's plan was chosen
+  // from (spf_query_create), the sources and the rows plan's node -> row map
+  // (host copies kept for the query's life: 4 nq bytes, and 4 V bytes under a
+  // rows, levels or few-rows plan), and the verdicts cached per graph generation (stale_why
+  // over the graph scalars, nbr_why over the neighbour lists; empty = holds)
+  struct {
+    bool exact = false, wrap = false, uniform = false, paired = true, links_patched = false;
+    uint32_t n_zero = 0, cw_bits = 0;
+    uint64_t zero_sig = 0, nbr_gen = 0;
+  } made;
+  std::vector<uint32_t> srcs;
+  std::vector<int32_t> row_of;
+  mutable uint64_t seen_gen = 0, seen_nbr_gen = 0;
+  mutable std::string stale_why, nbr_why;
   uint32_t nbig = 0;
   uint32_t nmid = 0;          // the first nmid of them have at most kNsHeldWide words
   // zero-metric plan (spf_zvar_kernel): variant tables, their closure pairs
@@ -9735,7 +9762,7 @@ struct spf_query {
   // pair zoff[zvars]), each source's variant, and the wide-plan run of the
   // sources with a metric-0 out-link (their first hop costs 0, outside the
   // byte rule) whose rows replace this query's rows zfix_rows
-  uint32_t zvars = 0, zscale = 0, znlinks = 0;
+  uint32_t zvars = 0, znlinks = 0; // (the level scale is read live: g->nz_uniform)
   std::vector<uint32_t> zoff;
   uint32_t* d_zl = nullptr;
   uint8_t* d_zvar = nullptr;
@@ -10862,6 +10889,25 @@ void set_lanes_per_node(spf_graph* g) {
   g->G = G;
 }
 
+// graphs with a metric 0 (the zero-metric plan's candidates): the one value
+// every other metric has
+void scan_nz_uniform(spf_graph* g) {
+  g->nz_uniform = 0;
+  if (!g->n_zero || g->wrap) {
+    return;
+  }
+  uint64_t c = 0;
+  for (const uint64_t m : g->w64) {
+    if (m && m != c) {
+      if (c) {
+        return;
+      }
+      c = m;
+    }
+  }
+  g->nz_uniform = (uint32_t)c; // (no wrap: below 2^31)
+}
+
 int upload_weights(spf_graph* g) {
   const uint32_t E = g->E, V = g->V;
   const unsigned nth = openr::hostThreads(E, kHostMinEdges);
@@ -10929,6 +10975,11 @@ int upload_weights(spf_graph* g) {
   g->n_zero = (uint32_t)zero_e.size();
   g->maxw = maxw;
   refresh_exact(g);
+  g->zero_sig = 0xcbf29ce484222325ull; // FNV-1a over the sorted list
+  for (const uint32_t e : zero_e) {
+    g->zero_sig = (g->zero_sig ^ e) * 0x100000001b3ull;
+  }
+  scan_nz_uniform(g);
   const bool exact = g->exact;
   // wide plan band: the mean metric (near-far's delta ~ a typical edge)
   g->wide_delta = E ? std::max<uint64_t>(1, sumw / E) : 1;
@@ -11134,6 +11185,7 @@ void rescan_scalars(spf_graph* g) {
   refresh_exact(g);
   g->wide_delta = E ? std::max<uint64_t>(1, sumw / E) : 1;
   g->uniform = (!g->exact && E && uni) ? (uint32_t)c0 : 0;
+  scan_nz_uniform(g);
 }
 
 int patch_weights_sparse(spf_graph* g, uint32_t n, const uint32_t* edge_idx, const uint64_t* m) {
@@ -11601,6 +11653,7 @@ int spf_graph_update(spf_graph* g, const spf_graph_desc* desc) {
     return vs;
   }
   mark("validate");
+  ++g->gen;
   const uint32_t V = desc->num_nodes, E = desc->num_edges;
   HIP_TRY(hipSetDevice(g->device));
   HIP_TRY(hipStreamSynchronize(g->stream)); // queued work reads the old arrays
@@ -11780,6 +11833,7 @@ int spf_graph_set_transit(spf_graph* g, const uint8_t* node_overloaded) {
   if (!g || (g->V && !node_overloaded)) {
     return fail(SPF_E_INVALID, "null argument");
   }
+  ++g->gen;
   std::fill(g->trbits.begin(), g->trbits.end(), 0u);
   for (uint32_t v = 0; v < g->V; ++v) {
     if (!node_overloaded[v]) {
@@ -11810,6 +11864,7 @@ int spf_graph_patch_metrics(
       return fail(SPF_E_INVALID, "edge index out of range");
     }
   }
+  ++g->gen;
   HIP_TRY(hipSetDevice(g->device));
   if (n && (uint64_t)n * 64 <= g->E && env_flag("OPENR_SPF_PATCH_INPLACE", 1)) {
     const int st = patch_weights_sparse(g, n, edge_idx, m);
@@ -11846,6 +11901,7 @@ int spf_graph_set_edges(
       return fail(SPF_E_UNSUPPORTED, "metric outside the in-place range (0, wrap or unpackable)");
     }
   }
+  ++g->gen;
   if (g->col_orig.empty()) {
     g->col_orig = g->col;
     g->edge_up.assign(g->E, 1);
@@ -12097,6 +12153,19 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
   q->has_ign = has_ign;
   q->Vp = (V + 15) & ~15u;
   q->Vp8 = (V + 15) & ~15u;
+  // what the plan below is chosen from (spf_query_stale compares them with
+  // the graph at run time)
+  q->made.exact = g->exact;
+  q->made.wrap = g->wrap;
+  q->made.uniform = g->uniform != 0;
+  q->made.paired = g->paired;
+  q->made.links_patched = g->links_patched;
+  q->made.n_zero = g->n_zero;
+  q->made.cw_bits = g->cw_bits;
+  q->made.zero_sig = g->zero_sig;
+  q->made.nbr_gen = q->seen_nbr_gen = g->nbr_gen;
+  q->seen_gen = g->gen;
+  q->srcs.assign(desc->sources, desc->sources + nq);
   auto bail = [&](int s) {
     free_query(q);
     return s;
@@ -12413,7 +12482,6 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
     // next hops: one table per variant; distances alone: one table closed
     // over every metric-0 half-edge
     q->zvars = want_nh ? (1u << zlinks.size()) : 1u;
-    q->zscale = zc;
     q->znlinks = (uint32_t)zlinks.size();
     std::vector<uint32_t> zl;
     for (uint32_t j = 0; j < q->zvars; ++j) {
@@ -12560,6 +12628,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
       }
     }
   }
+  q->row_of = std::move(row_of); // (spf_query_stale: which neighbours have a row)
   const size_t ntab = std::max<uint32_t>(1, q->zvars); // MS-BFS tables (zero-metric variants)
   if (q->dist == DistPlan::MsBfs) {
     if (pool_malloc((void**)&q->d_lvl, ntab * q->nrows * q->Vp8) != hipSuccess ||
@@ -13248,10 +13317,11 @@ int launch_msbfs(spf_query* q, bool unit) {
   a.Vp = q->Vp;
   a.Vp8 = q->Vp8;
   a.nq = q->nrows; // the batch + its helper sources
-  a.scale = unit ? 1u : (q->zvars ? q->zscale : g->uniform);
+  a.scale = unit ? 1u : (q->zvars ? g->nz_uniform : g->uniform);
   a.wrec = env_flag("OPENR_MS_WREC", 0); // measured slower (0.212 -> 0.232 ms, profiles/r03g)
   a.zlist = nullptr;
   a.nz = 0;
+  q->ms_scale = a.scale;
   a.lvl_only = lvl_only(q) ? 1u : 0u;
   a.blocked = q->d_ms_blocked;
   q->ms_par ^= 1u;
@@ -13427,7 +13497,7 @@ int launch_nh_levels(spf_query* q, bool unit) {
   a.Vp = q->Vp;
   a.Vp8 = q->Vp8;
   a.nq = q->nq;
-  a.scale = unit ? 1u : (q->zvars ? q->zscale : g->uniform);
+  a.scale = unit ? 1u : (q->zvars ? g->nz_uniform : g->uniform);
   a.zvar = q->d_zvar;
   a.lvl_vstride = (uint64_t)q->nrows * q->Vp8;
   a.dist_vstride = (uint64_t)q->nrows * q->Vp;
@@ -13633,17 +13703,9 @@ int finish_zero_plan(spf_query* q) {
 int run_screen(spf_query* q) {
   spf_query* b = q->base;
   spf_graph* g = q->g;
-  if (!q->wh_cand.empty() && !g->paired) {
-    // the source-link kernels were chosen for a graph whose half-edges were
-    // paired; spf_graph_set_edges has since taken one half of a link down
-    return fail(SPF_E_UNSUPPORTED,
-                "what-if query: a half-edge went down alone since creation (recreate the query)");
-  }
-  if (!q->wh_cand.empty() && !((q->flags & SPF_F_UNIT_METRIC) || g->uniform)) {
-    // the source-link kernels compute levels x the uniform metric
-    return fail(SPF_E_UNSUPPORTED,
-                "what-if query: the metrics stopped being uniform since creation (recreate the query)");
-  }
+  // (the source-link kernels need every half-edge paired and, without the
+  // unit flag, a uniform metric, as when they were chosen: spf_query_run
+  // refuses the query as stale once either ended)
   int s = SPF_OK;
   if (q->hop) {
     // the first-hop rows: BFS levels from the sources' neighbours through
@@ -14068,7 +14130,7 @@ int spf_query_pack_levels(spf_query* q, void* dst_dev, size_t dst_pitch, void* t
   }
   spf_graph* g = q->g;
   const bool have = has_level_rows(q) && q->nq && g->V;
-  const uint32_t scale = (q->flags & SPF_F_UNIT_METRIC) ? 1u : g->uniform;
+  const uint32_t scale = q->ms_scale; // of the run whose rows these are
   if (have && (!dst_dev || dst_pitch < g->V)) {
     return fail(SPF_E_INVALID, "level rows: no destination or pitch < V");
   }
@@ -14095,10 +14157,114 @@ int spf_query_pack_levels(spf_query* q, void* dst_dev, size_t dst_pitch, void* t
   return SPF_OK;
 }
 
+// ---- the life of a query across in-place graph changes ----
+//
+// spf_query_create fixes the plan from facts of the graph; the mutators can
+// move those facts under a live query.  The launch helpers read what they can
+// live (transit bits, metrics, the uniform value, the neighbour lists); what
+// follows names the facts they cannot, per plan.  Empty = the plan holds.
+
+// the neighbour lists were rebuilt (spf_graph_set_edges): every source keeps
+// its mask-width class and, where next hops come from rows, every neighbour
+// that is up has a row in the batch.  O(sum of the sources' neighbours).
+static std::string stale_nbr_reason(const spf_query* q) {
+  const spf_graph* g = q->g;
+  if (!(q->flags & SPF_F_NEXTHOPS)) {
+    return "";
+  }
+  const bool rows = (q->nh == NhPlan::Rows || q->nh == NhPlan::Levels) && !q->row_of.empty();
+  for (uint32_t i = 0; i < q->nq; ++i) {
+    const uint32_t s = q->srcs[i];
+    const uint32_t nn = g->nbr_off[s + 1] - g->nbr_off[s];
+    const uint32_t w = std::max<uint32_t>(1, (nn + 63) / 64);
+    const uint32_t b = (q->flags & kQueryWideMasks) ? 8 * w : nh_bytes_for(nn);
+    if (w != q->nh_w[i] || b != q->nh_b[i]) {
+      return "node " + std::to_string(s) + " now has " + std::to_string(nn) +
+             " neighbours: another next-hop mask width than its rows were laid out for";
+    }
+    for (uint32_t k = g->nbr_off[s]; rows && k < g->nbr_off[s + 1]; ++k) {
+      if (q->row_of[g->nbrs[k]] < 0) {
+        return "neighbour " + std::to_string(g->nbrs[k]) + " of node " + std::to_string(s) +
+               " came up after the batch was planned and has no row in it";
+      }
+    }
+  }
+  return "";
+}
+
+static std::string stale_reason(const spf_query* q) {
+  const spf_graph* g = q->g;
+  const auto& m = q->made;
+  if (m.paired && !g->paired) {
+    return "one half of a link went down alone";
+  }
+  if ((q->flags & SPF_F_ORDER) && g->links_patched && !m.links_patched) {
+    return "links were set in place under a settle-order query";
+  }
+  if (!(q->flags & SPF_F_UNIT_METRIC)) { // (a unit-metric plan reads no metric)
+    if (g->exact != m.exact) {
+      return g->exact ? "the graph now needs 64-bit rows" : "the graph no longer needs 64-bit rows";
+    }
+    if (g->wrap != m.wrap) {
+      return "wrapping metrics came or went";
+    }
+    if (g->n_zero != m.n_zero || g->zero_sig != m.zero_sig) {
+      return "the set of metric-0 half-edges changed";
+    }
+    if (m.uniform && !g->uniform) {
+      return "the metric stopped being uniform";
+    }
+    if (q->zvars && (!g->nz_uniform || (uint64_t)g->nz_uniform * g->V >= 0xFFFFFFFFull)) {
+      return "the zero-metric plan needs one nonzero metric value";
+    }
+    if ((q->dlds || q->dstep_pack) && g->cw_bits != m.cw_bits) {
+      return "the packed edge words changed or were freed";
+    }
+    if (q->dlds && g->maxw > kDlMaxDist) {
+      return "a metric left the LDS-row range";
+    }
+  }
+  if (g->nbr_gen != m.nbr_gen) {
+    if (q->seen_nbr_gen != g->nbr_gen) {
+      q->nbr_why = stale_nbr_reason(q);
+      q->seen_nbr_gen = g->nbr_gen;
+    }
+    return q->nbr_why;
+  }
+  return "";
+}
+
+// nullptr: the plan of q and of the sub-queries it owns holds.  One integer
+// compare per query while the graph's generation stands.
+static const char* query_stale_why(const spf_query* q) {
+  if (q->seen_gen != q->g->gen) {
+    q->stale_why = stale_reason(q);
+    q->seen_gen = q->g->gen;
+  }
+  if (!q->stale_why.empty()) {
+    return q->stale_why.c_str();
+  }
+  for (const spf_query* sub : {q->base, q->hop, q->zfix}) {
+    if (const char* why = sub ? query_stale_why(sub) : nullptr) {
+      return why;
+    }
+  }
+  return nullptr;
+}
+
+int spf_query_stale(const spf_query* q) {
+  return q && query_stale_why(q) ? 1 : 0;
+}
+
 int spf_query_run(spf_query* q) {
   SPF_ABI_RANGE("spf_query_run");
   if (!q) {
     return fail(SPF_E_INVALID, "null query");
+  }
+  if (const char* why = query_stale_why(q)) {
+    // nothing recorded, nothing launched: the last run's results stay readable
+    return fail(SPF_E_INVALID, std::string("stale query: ") + why +
+                                   " since spf_query_create (create a new query)");
   }
   spf_graph* g = q->g;
   HIP_TRY(hipSetDevice(g->device));
