@@ -2697,8 +2697,21 @@ __global__ __launch_bounds__(kNhThreads) void spf_nh_rows_kernel(NhRowsArgs a) {
 
 constexpr uint32_t kMsThreads = 1024;
 constexpr uint32_t kMsShallowLevel = 127;
-constexpr uint32_t kMsMaxK = 20; // nodes per thread -> V <= 20480 (32-bit batches above 10,240 nodes: the
-                                 // double buffer is 2 * V * 4 B <= 160 KB of LDS)
+constexpr uint32_t kMsMaxK = 20; // nodes per thread; with the LDS bound V <= 20,448 (32-bit batches above
+                                 // 10,224 nodes: the double buffer is 2 * V * 4 B, ms_fits)
+// every spf_msbfs_kernel instance holds static LDS beside the dynamic frontier
+// double buffer (the workgroup reduction behind __syncthreads_or: 256 B,
+// .group_segment_fixed_size of the code object), and a workgroup may hold
+// 160 KB in all: a launch with 2 * V * 8 = 163,840 B of dynamic LDS is refused.
+// ms_static_lds() reads the largest figure of the instances back from the
+// runtime, once per process; kMsStaticLds stands in where that query fails
+constexpr size_t kMsStaticLds = 256;
+size_t ms_static_lds();
+// a `bits`-wide MS-BFS batch fits: V <= 10,224 at 64 bits, V <= 20,448 at 32
+inline bool ms_fits(uint32_t V, uint32_t bits) {
+  return V <= kMsThreads * kMsMaxK &&
+         2 * (size_t)V * (bits / 8) + ms_static_lds() <= kLdsLimit;
+}
 
 struct MsBfsArgs {
   const uint32_t* row;
@@ -3049,6 +3062,50 @@ __global__ __launch_bounds__(kMsThreads) void spf_msbfs_kernel(MsBfsArgs a) {
       }
     }
     __syncthreads();
+  }
+}
+
+// static LDS of the instances launch_msbfs picks from (ms_fits): asked of the
+// runtime at the first planned batch, never on the launch path.  A property
+// of the code object, so the figure of whichever device is current serves
+// every device; kept only once every query succeeded (a failed one answers
+// kMsStaticLds and the next call asks again)
+size_t ms_static_lds() {
+  static std::atomic<size_t> cached{~(size_t)0};
+  if (const size_t c = cached.load(std::memory_order_relaxed); c != ~(size_t)0) {
+    return c;
+  }
+  {
+    size_t most = 0;
+    bool ok = true;
+    auto one = [&](const void* k) {
+      hipFuncAttributes fa{};
+      if (hipFuncGetAttributes(&fa, k) == hipSuccess) {
+        most = std::max(most, (size_t)fa.sharedSizeBytes);
+      } else {
+        (void)hipGetLastError();
+        ok = false;
+      }
+    };
+#define MS_ONE(MT, KM)                                            \
+  one((const void*)spf_msbfs_kernel<MT, KM, true, true>);         \
+  one((const void*)spf_msbfs_kernel<MT, KM, false, true>);        \
+  one((const void*)spf_msbfs_kernel<MT, KM, true, false>);        \
+  one((const void*)spf_msbfs_kernel<MT, KM, false, false>)
+    MS_ONE(uint64_t, 4);
+    MS_ONE(uint64_t, 8);
+    MS_ONE(uint64_t, 10);
+    MS_ONE(uint32_t, 4);
+    MS_ONE(uint32_t, 8);
+    MS_ONE(uint32_t, 12);
+    MS_ONE(uint32_t, 16);
+    MS_ONE(uint32_t, 20);
+#undef MS_ONE
+    if (!ok) {
+      return kMsStaticLds;
+    }
+    cached.store(most, std::memory_order_relaxed);
+    return most;
   }
 }
 
@@ -12221,7 +12278,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
   std::vector<ZeroLink> zlinks;
   uint32_t zc = 0;
   const bool zcand = !unit && !literal && !want_order && !has_ign && g->exact && g->n_zero &&
-                     nq >= 32 && V <= kMsThreads * kMsMaxK && 2 * (size_t)V * 4 <= kLdsLimit &&
+                     nq >= 32 && ms_fits(V, 32) &&
                      env_flag("OPENR_SPF_ZERO_MSBFS", 1) &&
                      env_msbfs_width() != 0 &&
                      zero_plan_links(g, zlinks, zc);
@@ -12255,8 +12312,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
     // one source and its neighbours' rows in one MS-BFS pass beat the
     // single-workgroup SSSP of that source, e.g. a what-if baseline)
     const bool msbfs_candidate = !rows_ok && uniform && !literal &&
-                                 V <= kMsThreads * kMsMaxK &&
-                                 2 * (size_t)V * 4 <= kLdsLimit &&
+                                 ms_fits(V, 32) &&
                                  env_msbfs_width() != 0 &&
                                  env_flag("OPENR_SPF_MSBFS_HELPERS", 1);
     if (msbfs_candidate) {
@@ -12435,7 +12491,7 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
   // half-edges instead of one SSSP workgroup per query (OPENR_SPF_MSBFS_IGN=0
   // disables).  Mask memory: 8 B per (batch, half-edge), at most 1 GiB.
   if (has_ign && uniform && !want_nh && !want_order && !literal && !exact && nq >= 32 &&
-      V <= kMsThreads * kMsMaxK && helpers.empty() &&
+      ms_fits(V, 32) && helpers.empty() &&
       (q->dist == DistPlan::SsspLds || q->dist == DistPlan::SsspGmem) &&
       env_flag("OPENR_SPF_MSBFS_IGN", 1) &&
       env_msbfs_width() != 0 &&
@@ -12447,12 +12503,12 @@ int spf_query_create(spf_graph* g, const spf_query_desc* desc, spf_query** out) 
   // many sources on a uniform metric: bit-parallel multi-source BFS
   // (OPENR_SPF_MSBFS=0 disables, =32 / =64 picks the batch width)
   if ((q->dist == DistPlan::BfsLds || q->dist == DistPlan::BfsGmem) &&
-      V <= kMsThreads * kMsMaxK && (nq + helpers.size() >= 32 || !helpers.empty())) {
+      ms_fits(V, 32) && (nq + helpers.size() >= 32 || !helpers.empty())) {
     int width = env_msbfs_width();
-    if (width == 64 && 2 * (size_t)V * 8 > kLdsLimit) {
+    if (width == 64 && !ms_fits(V, 64)) {
       width = 32; // the 64-bit frontier double buffer does not fit LDS
     }
-    if ((width == 32 || width == 64) && 2 * (size_t)V * (width / 8) <= kLdsLimit) {
+    if ((width == 32 || width == 64) && ms_fits(V, (uint32_t)width)) {
       q->dist = DistPlan::MsBfs;
       q->ms_bits = width;
       q->lds_bytes = 2 * (size_t)V * (width / 8); // frontier double buffer
@@ -13343,10 +13399,12 @@ int launch_msbfs(spf_query* q, bool unit) {
   }
   const uint32_t K = (g->V + kMsThreads - 1) / kMsThreads;
   const void* kern = nullptr;
+  uint32_t kmax = 0;
   // the general instance (ignore masks, wave-recorded levels and zero-metric
   // closure compiled in) only for the batches that need one of them
   const bool gen = q->ms_ign || a.wrec || q->zvars;
 #define MS_PICK(MT, KM)                                                                      \
+  kmax = KM;                                                                                 \
   kern = gen ? (sell ? (const void*)spf_msbfs_kernel<MT, KM, true, true>                     \
                      : (const void*)spf_msbfs_kernel<MT, KM, false, true>)                   \
              : (sell ? (const void*)spf_msbfs_kernel<MT, KM, true, false>                    \
@@ -13359,10 +13417,10 @@ int launch_msbfs(spf_query* q, bool unit) {
     } else if (K <= 10) {
       // the 10k fabric (K = 10): the plain instance spills 2 VGPRs, not 24
       MS_PICK(uint64_t, 10);
-    } else if (K <= 12) {
-      MS_PICK(uint64_t, 12);
     } else {
-      MS_PICK(uint64_t, 16);
+      // spf_query_create narrows the batch to 32 sources once the 64-bit
+      // frontier double buffer no longer fits LDS (ms_fits: V > 10,224)
+      return fail(SPF_E_INVALID, "internal: 64-bit MS-BFS batch past 10,224 nodes");
     }
   } else {
     if (K <= 4) {
@@ -13437,6 +13495,14 @@ int launch_msbfs(spf_query* q, bool unit) {
   HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)q->lds_bytes));
   const uint32_t ntab = std::max<uint32_t>(1, q->zvars);
+  if (env_flag("OPENR_SPF_CREATE_TIMING", 0)) { // which instance ran (tests read this line)
+    std::fprintf(stderr,
+                 "[launch_msbfs] bits=%d kmax=%u sell=%d gen=%d grid=%u nbatch=%u blocked=%d "
+                 "tables=%u\n",
+                 q->ms_bits, kmax, sell ? 1 : 0, gen ? 1 : 0, q->grid,
+                 (q->nrows + (uint32_t)q->ms_bits - 1) / (uint32_t)q->ms_bits,
+                 a.blocked ? 1 : 0, ntab);
+  }
   for (uint32_t j = 0; j < ntab; ++j) {
     if (q->zvars) { // zero-metric variant j: its own table and closure pairs
       a.dist_out = (uint32_t*)q->d_dist + (size_t)j * q->nrows * q->Vp;
@@ -14076,7 +14142,7 @@ extern "C" {
 // equal on every rank.
 __attribute__((visibility("hidden"))) int spf_graph_levels_capable_(
     const spf_graph* g, uint32_t unit) {
-  if (!g || g->V > kMsThreads * kMsMaxK || 2 * (size_t)g->V * 4 > kLdsLimit) {
+  if (!g || !ms_fits(g->V, 32)) {
     return 0;
   }
   if (unit || g->uniform != 0) {

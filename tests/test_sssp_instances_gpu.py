@@ -20,9 +20,9 @@ WMAX 1 / 4 / 16) and the flags and ignore lists the batch was created with.
      LDS state one query leaves is the state the next one starts from.
 
 One planner fact the cases are laid out around: a unit-metric batch with next
-hops and no ignore list takes the MS-BFS plan whenever V <= 20,480 (the
+hops and no ignore list takes the MS-BFS plan whenever V <= 20,448 (the
 batch's neighbours ride along as helper sources), so spf_sssp_kernel<W, UNIT,
-no IGN> on the LDS plan is reachable only for 20,480 < V <= ~25,680.  Those
+no IGN> on the LDS plan is reachable only for 20,448 < V <= ~25,680.  Those
 cells of the matrix run on a 21,000-node graph; every other LDS cell runs on
 the 420-node graph.
 """
@@ -164,7 +164,7 @@ def dense(gpu_ready):
 
 @pytest.fixture(scope="module")
 def mid(gpu_ready):
-    """Past the MS-BFS plan's 20,480 nodes, within the LDS plan's image."""
+    """Past the MS-BFS plan's 20,448 nodes, within the LDS plan's image."""
     net = hub_net(103, 21000, 45000, 1, 20)
     yield net
     net.g.close()
